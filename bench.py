@@ -3,6 +3,10 @@ headline, and the other configs as secondary legs in the same JSON line.
 
 python bench.py --gpus N --steps K --warmup W      (N>1: launched by torch.distributed.run)
 
+A plain run measures the headline alone: set-up, warmup, the K timed steps, the JSON line.  --full adds
+everything else (the secondary legs, the CPU baselines, the detail file); --dump-outputs DIR writes the
+last timed step's records as .npy files (dump_outputs).
+
 Headline step = one pass of the hot path over one batch: 4096 start/goal pairs on the C2 grid
 (SURVEY.md §8(d) generator), inputs resident in HBM, outputs (cost, path, n_expanded, status)
 written to HBM.  Secondary legs (--legs): the H=30 x 4096-sample control step (C4, DWA form), RRT*
@@ -480,6 +484,28 @@ def check_timed(name, ref: dict, outs) -> int:
     if n == 0:
         raise AssertionError(f"{name}: no timed output to check")
     return n
+
+
+DUMP_PATH_ROWS = 1024  # queries whose paths --dump-outputs keeps (f32, path_cap wide: 16 MB at 4096)
+
+
+def dump_outputs(dirname, o: dict):
+    """--dump-outputs DIR: the records of the last timed step's batch, as a caller of the planner
+    receives them, one DIR/<name>.npy each: cost, path_len, n_expanded, status (f64, every query) and
+    path (f32: the cell indices, below 2^24 so exact) for DUMP_PATH_ROWS queries drawn with
+    default_rng(0) (path_rows.npy holds their indices); path entries past path_len, which the planner
+    leaves unwritten, are stored as -1.  The inputs are seeded, so two builds give equal files."""
+    os.makedirs(dirname, exist_ok=True)
+    n = len(o["cost"])
+    rows = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_PATH_ROWS), replace=False))
+    plen = o["plen"].cpu().numpy()
+    path = o["path"][rows.tolist()].cpu().numpy().astype(np.float32)
+    path[np.arange(path.shape[1])[None, :] >= plen[rows, None]] = -1.0
+    arrays = {"cost": o["cost"].cpu().numpy(), "path_len": plen, "n_expanded": o["nexp"].cpu().numpy(),
+              "status": o["status"].cpu().numpy(), "path_rows": rows}
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v.astype(np.float64))
+    np.save(os.path.join(dirname, "path.npy"), path)
 
 
 def cgroup_cpus():
@@ -1833,6 +1859,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the secondary legs (--legs), the CPU baselines and the "
+                         "detail file; without it only the headline is set up, warmed up, timed and printed")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step (batch) returned as DIR/<name>.npy "
+                         "(f64; the paths as an f32 sample of fixed rows): see dump_outputs")
     ap.add_argument("--strong-share", default="",
                     help="diagnostic R/N: rank R's share of C2 under the N-rank strong split on this GPU (c2_share_mode)")
     ap.add_argument("--tail-sq", type=int, default=0,
@@ -1869,9 +1901,10 @@ def main():
     ap.add_argument("--residency", type=int, default=0,
                     help="A* queries resident per CU over all batches in flight (sets each one's LDS heap share; "
                          "0 = the engine's default)")
-    ap.add_argument("--legs", default="dwa,rrt,astar3d,totp,lqr,mpc,graphs,dstar,dyn3d,latency",
-                    help="secondary legs to run (comma list of dwa, rrt, astar3d, totp (C5 trajectories on the "
-                         "astar3d leg's paths), lqr, mpc, graphs, dstar, dyn3d, latency; 'none' for none)")
+    ap.add_argument("--legs", default=None,
+                    help="with --full: secondary legs to run (comma list of dwa, rrt, astar3d, totp (C5 trajectories "
+                         "on the astar3d leg's paths), lqr, mpc, graphs, dstar, dyn3d, latency; 'none' for none; "
+                         "default: all of them)")
     ap.add_argument("--dyn3d-queries", type=int, default=8192, help="C5 queries per DStar3D / LPAStar3D launch")
     ap.add_argument("--dyn3d-steps", type=int, default=24)
     ap.add_argument("--dyn3d-streams", type=int, default=4, help="DStar3D / LPAStar3D launches in flight")
@@ -1948,6 +1981,14 @@ def main():
                     help="no GPU: exercise the rank launcher, the strong-scaling deal and the result all_gather "
                          "over gloo with the CPU oracle standing in for the kernels (tests/test_multirank.py)")
     args = ap.parse_args()
+    # a plain run is the headline alone; the secondary legs and the CPU baselines take runs of their own
+    if args.full:
+        args.legs = args.legs or "dwa,rrt,astar3d,totp,lqr,mpc,graphs,dstar,dyn3d,latency"
+    else:
+        if args.legs not in (None, "", "none"):
+            ap.error("--legs needs --full")
+        args.legs = "none"
+        args.no_cpu_baseline = True
     # engine defaults: engine 1 (multi-query, one heap operation per group per step, two-level spill
     # blocks) -- 15,360 groups in flight, 60 per CU = 3.75 waves per SIMD (round 4, same box,
     # alternating, three rounds: 56 / 60 / 64 per CU 17.38-17.41 k / 17.70-17.82 k / 16.69-18.06 k
@@ -2102,6 +2143,9 @@ def main():
         last_nb = nbs[max(i for i in range(nlaunch) if i % S == li)]
         outs += [{k: b[k][j * nq:(j + 1) * nq] for k in ("cost", "plen", "nexp", "status")} for j in range(last_nb)]
     timed_checked = check_timed("astar2d", ref_out, outs)
+    if args.dump_outputs and rank == 0:
+        b, j = lanes[(nlaunch - 1) % S], nbs[-1] - 1  # the last timed step: the last batch of the last launch
+        dump_outputs(args.dump_outputs, {k: b[k][j * nq:(j + 1) * nq] for k in ("cost", "plen", "path", "nexp", "status")})
     elapsed, kern_ms, span_ms = shard.max_over_ranks(dist, [elapsed, kern_ms, span_ms], "cuda")
     # the ranks plan different pair sets (weak: default_rng(1 + rank); strong: dealt shares): the roofline
     # is per GPU, on the mean over ranks of each rank's own algorithmic bytes against the max-over-ranks
@@ -2231,7 +2275,7 @@ def main():
                        "timed_launches_checked": timed_checked},
             "launch_manifest": _MANIFEST,
         }
-        path = write_detail(args, out)
+        path = write_detail(args, out) if args.full or args.detail_out else None
         line = json.dumps(headline_line(out, path))
         print(line, flush=True)
     if dist:

@@ -11,7 +11,7 @@ if [ -n "$TESTS" ]; then
   rc=$?; tail -2 $O.test.log; [ $rc -eq 0 ] || exit $rc
 fi
 if [ -n "$LEGS" ]; then
-  timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py --legs $LEGS --no-cpu-baseline --steps ${STEPS:-1} --warmup 1 \
+  timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py --full --legs $LEGS --no-cpu-baseline --steps ${STEPS:-1} --warmup 1 \
       --detail-out $O.detail.json $BENCH_ARGS > $O.bench.json 2> $O.bench.err || { tail -5 $O.bench.err; exit 1; }
   python3 - "$O.bench.json" <<'PY'
 import json, sys

@@ -11,7 +11,7 @@ S2="SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INS
 i=0
 for set in "$S1" "$S2"; do
   i=$((i+1))
-  timeout -s KILL 200 rocprofv3 --pmc $set -d $OUT/p$i -o run -- python3 $R/bench.py --legs $LEG --no-cpu-baseline --steps 1 --warmup 1 $EXTRA > $OUT/p$i.log 2>&1 || { echo "pass $i failed"; tail -5 $OUT/p$i.log; exit 1; }
+  timeout -s KILL 200 rocprofv3 --pmc $set -d $OUT/p$i -o run -- python3 $R/bench.py --full --legs $LEG --no-cpu-baseline --steps 1 --warmup 1 $EXTRA > $OUT/p$i.log 2>&1 || { echo "pass $i failed"; tail -5 $OUT/p$i.log; exit 1; }
 done
 python3 - $OUT $KER <<'PY'
 import glob, sqlite3, sys

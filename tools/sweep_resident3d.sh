@@ -6,7 +6,7 @@ O=$R/gpurun_out/res3d
 mkdir -p $O
 run() {  # name, bench args...
   n=$1; shift
-  timeout -k 10 240 python3 $R/bench.py --no-cpu-baseline --steps 1 --warmup 1 "$@" > $O/$n.json 2> $O/$n.err || exit 1
+  timeout -k 10 240 python3 $R/bench.py --full --no-cpu-baseline --steps 1 --warmup 1 "$@" > $O/$n.json 2> $O/$n.err || exit 1
   python3 - $O/$n.json $n <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
