@@ -125,6 +125,30 @@ int pmp_graph3d_batch(pmp_ctx* ctx, void* stream, int algo, const uint32_t* occ_
                       int32_t* path_len, uint32_t* path, int path_cap, int32_t* n_expanded, uint32_t* expand,
                       int expand_cap, int64_t* counters, int32_t* status);
 
+/*
+ * Batched 3D Jump Point Search.  Replaces JPS3D.plan (global_planner/graph_search/jps3d.py:42-88):
+ * AStar3D's loop and (f, h, counter) heap with the 26 jump() results (:96-155, forced neighbours
+ * :164-244, isCollision graph_search_3d.py:66-107 with Python-int coordinates) as the neighbour set,
+ * g(jump point) = g(node) + math.sqrt of the integer square distance (_mk_qnode, :158-160), cost
+ * and path by extractPath over CLOSED parents (:248-261); the path lists jump points only.  jump()
+ * is evaluated in its collapsed form (csrc/jps3d.hip): a plane-diagonal jump returns the adjacent
+ * cell whenever a goal / forced / axis-jump step lies on its ray, a space-diagonal jump the first
+ * such step or the first from which a plane-diagonal jump succeeds.
+ * Arguments and statuses as pmp_graph3d_batch (inf cost, status 1, path_len 0 when OPEN empties or
+ * an endpoint lies outside the grid), and:
+ *   expand         nullable [nq][expand_cap] u32 CLOSED cells in first-insertion order
+ *   expand_parent  nullable [nq][expand_cap] u32 the final CLOSED parent cell of each of those cells
+ *                  (after any re-expansion; the start's parent is the start); needs expand
+ *   expand_g       nullable [nq][expand_cap] f64 their final CLOSED g; needs expand
+ *   counters       nullable [nq][4] i64 the reference's pushes, pops, expansions (incl. re-expansions),
+ *                  max heap size
+ * PMP_CAP_OVERFLOW when the heap or the push counter (64 per cell) overflows.
+ */
+int pmp_jps3d_batch(pmp_ctx* ctx, void* stream, const uint32_t* occ_bits, int per_query, int X, int Y, int Z,
+                    int heuristic, const int32_t* start_xyz, const int32_t* goal_xyz, int nq, double* cost,
+                    int32_t* path_len, uint32_t* path, int path_cap, int32_t* n_expanded, uint32_t* expand,
+                    uint32_t* expand_parent, double* expand_g, int expand_cap, int64_t* counters, int32_t* status);
+
 /* LocalPlanner.params (local_planner/local_planner.py:39-55), same names and units. */
 typedef struct {
     double dt;             /* TIME_STEP */

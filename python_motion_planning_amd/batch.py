@@ -556,6 +556,43 @@ def astar3d_batch(occ, starts, goals, heuristic: str = "euclidean", path_cap: in
     return out
 
 
+def jps3d_batch(occ, starts, goals, heuristic: str = "euclidean", path_cap: int | None = None,
+                expand_cap: int = 0, counters: bool = False):
+    """Batched JPS3D.plan (jps3d.py:42-88) on pmp_jps3d_batch (csrc/jps3d.hip).
+
+    occ: uint8 [X, Y, Z] shared grid or [nq, X, Y, Z] per-query grids (numpy).
+    Returns astar3d_batch's dict (the path lists jump points only; n_expanded = len(CLOSED)) and, with
+    expand_cap != 0, expand_parent / expand_g [nq, expand_cap]: the final CLOSED parent cell and g of
+    the cells in `expand`.
+    """
+    torch = _lib.device_check()
+    L = _lib.load_library()
+    ctx = _lib.context()
+    occ_bits, per_query, (X, Y, Z) = _occ3d_bits(torch, occ)
+    s = _dev(torch, starts, torch.int32).reshape(-1, 3)
+    g = _dev(torch, goals, torch.int32).reshape(-1, 3)
+    nq = int(s.shape[0])
+    if path_cap is None:
+        path_cap = min(X * Y * Z + 1, 1 << 16)
+    i32 = dict(dtype=torch.int32, device="cuda")
+    out = dict(cost=torch.empty(nq, dtype=torch.float64, device="cuda"), path_len=torch.empty(nq, **i32),
+               path=torch.empty((nq, path_cap), **i32), n_expanded=torch.empty(nq, **i32),
+               status=torch.empty(nq, **i32))
+    out["expand"] = torch.empty((nq, expand_cap), **i32) if expand_cap else None
+    out["expand_parent"] = torch.empty((nq, expand_cap), **i32) if expand_cap else None
+    out["expand_g"] = torch.empty((nq, expand_cap), dtype=torch.float64, device="cuda") if expand_cap else None
+    out["counters"] = torch.empty((nq, 4), dtype=torch.int64, device="cuda") if counters else None
+    rc = L.pmp_jps3d_batch(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), 1 if per_query else 0, X, Y, Z,
+                           1 if heuristic == "manhattan" else 0, s.data_ptr(), g.data_ptr(), nq,
+                           out["cost"].data_ptr(), out["path_len"].data_ptr(), out["path"].data_ptr(), int(path_cap),
+                           out["n_expanded"].data_ptr(), _lib.ptr(out["expand"]), _lib.ptr(out["expand_parent"]),
+                           _lib.ptr(out["expand_g"]), int(expand_cap), _lib.ptr(out["counters"]),
+                           out["status"].data_ptr())
+    _lib.check(ctx, rc, "pmp_jps3d_batch")
+    out["dims"] = (X, Y, Z)
+    return out
+
+
 def dstar3d_batch(occ, starts, goals, blocks=None, path_cap: int | None = None, expand_cap: int = 0,
                   max_process: int = 0, occ_bits=None):
     """Batched DStar3D (d_star3d.py:60-281): plan() and then one apply_dynamic_obstacles() per round

@@ -464,6 +464,52 @@ class LazyThetaStar3D(AStar3D):
         return "Lazy Theta* 3D"
 
 
+class JPS3D(GraphSearcher3D):
+    """Jump Point Search for 3D grids (jps3d.py:25-261) -- the search runs in the gfx950 kernel
+    jps3d.hip.  Coordinates are taken as Python ints: with numpy integers the reference's isCollision
+    (graph_search_3d.py:91) adds np.bool_s and skips the corner cells, which is another planner."""
+
+    def __init__(self, start: tuple, goal: tuple, env, heuristic_type: str = "euclidean") -> None:
+        super().__init__(tuple(int(v) for v in start), tuple(int(v) for v in goal), env, heuristic_type)
+        self.start.g = 0.0
+        self.start.h = self.h(self.start, self.goal)
+
+    def __str__(self) -> str:
+        return "Jump Point Search (JPS) 3D"
+
+    def plan(self) -> tuple:
+        """(cost, path start->goal, expand) -- (inf, [], expand) when unreachable (jps3d.py:42-88).  The
+        path lists jump points; expand is list(CLOSED.values()): Node3D(current, parent, g, h) per
+        CLOSED cell in first-insertion order, parent and g the final ones, h computed here."""
+        from .env import Node3D
+
+        occ = self.env.occupancy()
+        X, Y, Z = occ.shape
+        r = batch.jps3d_batch(occ, np.array([self.start.current]), np.array([self.goal.current]),
+                              self.heuristic_type, path_cap=X * Y * Z + 1, expand_cap=X * Y * Z)
+        st = int(r["status"][0])
+        ne = int(r["n_expanded"][0])
+        dec = lambda c: (int(c) // (Y * Z), (int(c) // Z) % Y, int(c) % Z)  # noqa: E731
+        ex = r["expand"][0, :ne].cpu().numpy()
+        ep = r["expand_parent"][0, :ne].cpu().numpy()
+        eg = r["expand_g"][0, :ne].cpu().numpy()
+        expand = []
+        for c, p, g in zip(ex, ep, eg):
+            node = Node3D(dec(c), dec(p), float(g), 0)
+            node.h = self.h(node, self.goal)
+            expand.append(node)
+        if st == 1:
+            return float("inf"), [], expand
+        if st != 0:
+            raise RuntimeError(f"{self} kernel status {st}")
+        cells = r["path"][0, : int(r["path_len"][0])].cpu().numpy()
+        return float(r["cost"][0]), [dec(c) for c in cells], expand
+
+    @classmethod
+    def plan_batch(cls, occ, starts, goals, heuristic_type: str = "euclidean", **kw):
+        return batch.jps3d_batch(occ, starts, goals, heuristic_type, **kw)
+
+
 class DNode3D:
     """D* bookkeeping node of DStar3D (d_star3d.py:21-57): coordinates in `current`, parent
     coordinates, tag t, h and k.  Equality and hashing by coordinates (Node3D, node3d.py:43-57)."""
