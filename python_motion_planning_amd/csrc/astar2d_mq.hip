@@ -121,24 +121,6 @@ __device__ __forceinline__ double bcf(double v)
     const uint64_t b = (uint64_t)__double_as_longlong(v);
     return __longlong_as_double(((uint64_t)bc<K>((uint32_t)(b >> 32)) << 32) | bc<K>((uint32_t)b));
 }
-__device__ __forceinline__ uint32_t shl1(uint32_t v)  // lane + 1 of my row (row_shl:1; lane 15 gets 0)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xF, 0xF, false);
-}
-__device__ __forceinline__ uint32_t shr1(uint32_t v)  // lane - 1 of my row (row_shr:1; lane 0 gets 0)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);
-}
-__device__ __forceinline__ double shr1f(double v)
-{
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    return __longlong_as_double(((uint64_t)shr1((uint32_t)(b >> 32)) << 32) | shr1((uint32_t)b));
-}
-__device__ __forceinline__ double shl1f(double v)
-{
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    return __longlong_as_double(((uint64_t)shl1((uint32_t)(b >> 32)) << 32) | shl1((uint32_t)b));
-}
 __device__ __forceinline__ uint32_t ror_or(uint32_t v)  // OR over my row
 {
     v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x121, 0xF, 0xF, false);
@@ -174,41 +156,27 @@ __device__ __forceinline__ void wave_sync_mem() { __builtin_amdgcn_fence(__ATOMI
 struct GHeap {
     lds_f64* F;      // LDS f[cap]
     lds_u32* C;      // LDS cm[cap]
-    lds_u32* K;      // LDS hkey[cap] (kKeys)
     lds_u32* B;      // LDS bit words: tier 0 (word 0), tier 1 (words 1..32)[, tier-2 bytes from word 36]
     uint32_t* T2;    // HBM tier-2 words (when not in LDS)
     __amdgpu_buffer_rsrc_t spill;  // the wave's spill region (4 groups)
-    uint32_t sbase;  // byte offset of heap position 0 in the spill region (mod 2^32): positions >= cap are spilled
-    uint32_t gbase;  // kBlocks: this group's byte offset in the wave's spill region
-    int L0;          // kBlocks: level of position cap (the first level with spilled positions)
-    int cap;
+    uint32_t gbase;  // this group's byte offset in the wave's spill region
+    int L0;          // level of position cap (the first level with spilled positions)
+    int cap;         // positions >= cap are spilled
     __amdgpu_buffer_rsrc_t mirror;  // kMirror: the mirror of the wave's spill region
 };
 constexpr uint32_t kOOR = 0x80000000u;  // a buffer offset beyond any spill region: loads 0, stores dropped
-#ifndef PMP_MQ_SPILL_SHIFT
-#define PMP_MQ_SPILL_SHIFT 1
-#endif
-constexpr int kSpillShift = PMP_MQ_SPILL_SHIFT;  // empty slots in front of position cap
-// Keep each entry's h order key (hkey) beside it: an LDS array (16 B per LDS position instead of 12)
-// and the spill record's fourth word, so loaded entries need no key rebuild (A/B switch)
-#ifndef PMP_MQ_KEYS
-#define PMP_MQ_KEYS 0
-#endif
-constexpr bool kKeys = PMP_MQ_KEYS != 0;
-constexpr int kEntLds = kKeys ? 16 : 12;  // LDS bytes per heap position
-// Spill layout: two-level blocks (default): from level L0 (position cap's level) down, bands of two
+// LDS bytes per heap position (f, cm); an entry's h order key (hkey) is rebuilt from its code when it
+// is loaded (a stored copy -- 16 B per LDS position, the spill record's fourth word -- was tried as a
+// build switch and not adopted)
+constexpr int kEntLds = 12;
+// Spill layout: two-level blocks: from level L0 (position cap's level) down, bands of two
 // levels; the block of a node Q at the level above a band holds Q's two children and four
 // grandchildren (6 x 16 B in one 128-B line), so a path and its siblings touch one line per two
-// spilled levels instead of one per level (round 4, same-box A/B: 15.5 k -> 16.6-17.1 k plans/s,
-// FETCH -18 %, WRITE -14 %).  Round 5 default (PMP_MQ_BLOCKS=2): each child with its own two
+// spilled levels instead of one per level (round 4, same-box A/B against position order: 15.5 k ->
+// 16.6-17.1 k plans/s, FETCH -18 %, WRITE -14 %).  Since round 5 each child sits with its own two
 // children in one 64-B half of the block, so a rotation's two stores per band dirty one half
-// (write-back sectors) instead of both -- WRITE -7 % at the same plans/s (profiles/r5/attribution.txt);
-// 1: the round-4 order [c0 c1 g00 g01 g10 g11]; 0: position order, sibling pairs 32-B aligned.
-#ifndef PMP_MQ_BLOCKS
-#define PMP_MQ_BLOCKS 2
-#endif
-constexpr bool kBlocks = PMP_MQ_BLOCKS != 0;
-constexpr bool kBlocks2 = PMP_MQ_BLOCKS == 2;
+// (write-back sectors) instead of both -- WRITE -7 % at the same plans/s against the round-4 order
+// [c0 c1 g00 g01 g10 g11] (profiles/r5/attribution.txt).
 // Write-traffic attribution (dev builds only, tools/build_variant.sh): every store of the selected
 // categories is issued twice, the copy into a mirror region with the same layout, so the extra
 // WRITE_SIZE over the default build is that category's write traffic.  Bits: 1 the trivial-push run's
@@ -218,26 +186,11 @@ constexpr bool kBlocks2 = PMP_MQ_BLOCKS == 2;
 #ifndef PMP_MQ_MIRROR
 #define PMP_MQ_MIRROR 0
 #endif
-// path_op's level shift: ds_bpermute from the group's direction (1, default: +0.8 % plans/s on the
-// VALU-bound step, three alternating rounds in tools/r5_call18.sh) or both DPP row shifts (0)
-#ifndef PMP_MQ_BPERM
-#define PMP_MQ_BPERM 1
-#endif
 constexpr int kMirror = PMP_MQ_MIRROR;
-// Push pairs (round 6): a group whose next two pending pushes land at sibling positions (n, n + 1
-// with n odd) runs both in one path operation -- the second _siftdown walks the same ancestors.
-// Parity-green (tests/test_heap_path_form.py models it against heapq; the GPU suite passed with it
-// on) but neutral on the headline: 19,129 vs 19,167 plans/s without (tools/calls/r6_call13.sh,
-// interleaved): 7 % fewer path operations, each heavier, on a step that waits on memory.  Off.
-#ifndef PMP_MQ_PAIR
-#define PMP_MQ_PAIR 0
-#endif
-constexpr bool kPair = PMP_MQ_PAIR != 0;
 
 // byte offset of spilled heap position p (>= cap) in the wave's spill region
 __device__ __forceinline__ uint32_t spill_off(const GHeap& h, int p)
 {
-    if (!kBlocks) return h.sbase + (uint32_t)p * 16u;
     const uint32_t u = (uint32_t)p + 1u;
     const int lam = (31 - __clz((int)u)) - h.L0;  // level below L0 (>= 0 for a spilled position)
     const int o = lam & 1, b = lam >> 1;
@@ -246,10 +199,9 @@ __device__ __forceinline__ uint32_t spill_off(const GHeap& h, int p)
     // blk = Q - 2^(L0-1) (2 4^b + 1) / 3, and (2 4^b + 1) / 3 = 1, 3, 11, 43, 171 for b = 0..4
     const uint32_t kb = (uint32_t)(0xAB2B0B0301ull >> (8 * b)) & 0xFFu;
     const uint32_t blk = Q - (kb << (h.L0 - 1));
-    // kBlocks 1: [c0 c1 g00 g01 g10 g11]; kBlocks 2: [c0 g00 g01 -][c1 g10 g11 -] (a child and its
-    // two children in one 64-B half: a path writes one half of a block)
-    const uint32_t slot = kBlocks2 ? (o ? ((u >> 1) & 1u) * 4u + 1u + (u & 1u) : (u & 1u) * 4u)
-                                   : (u & ((2u << o) - 1u)) + 2u * (uint32_t)o;
+    // [c0 g00 g01 -][c1 g10 g11 -] (a child and its two children in one 64-B half: a path writes one
+    // half of a block)
+    const uint32_t slot = o ? ((u >> 1) & 1u) * 4u + 1u + (u & 1u) : (u & 1u) * 4u;
     return h.gbase + blk * 128u + slot * 16u;
 }
 
@@ -258,12 +210,8 @@ __device__ __forceinline__ uint32_t spill_off(const GHeap& h, int p)
 // level L (lane_cw, computed once) and a position at level K takes lane K's word (a DPP / bpermute,
 // not ~20 VALU instructions of clz and 64-bit shifts): spill_off_cw.  A path operation's lanes hold
 // the path's levels in order, so each uses its own word; a node's sibling sits in the next 16-B slot
-// of the same block (offset ^ 16) -- with an odd LDS cap (GHeap.cap), sibling pairs never straddle
+// of the same block (offset ^ sib_xor) -- with an odd LDS cap (GHeap.cap), sibling pairs never straddle
 // the LDS / spill boundary.
-#ifndef PMP_MQ_LANECONST
-#define PMP_MQ_LANECONST 1
-#endif
-constexpr bool kLaneConst = PMP_MQ_LANECONST != 0 && kBlocks;
 __device__ __forceinline__ uint32_t lane_cw(int L0, int level)
 {
     const int lam = level - L0;
@@ -277,20 +225,17 @@ __device__ __forceinline__ uint32_t spill_off_cw(const GHeap& h, uint32_t cw, in
     const uint32_t u = (uint32_t)p + 1u;
     const uint32_t o = cw & 1u;
     const uint32_t blk = (u >> (o + 1u)) - (cw >> 1);
-    const uint32_t slot = kBlocks2 ? (o ? ((u >> 1) & 1u) * 4u + 1u + (u & 1u) : (u & 1u) * 4u)
-                                   : (u & ((2u << o) - 1u)) + 2u * o;
+    const uint32_t slot = o ? ((u >> 1) & 1u) * 4u + 1u + (u & 1u) : (u & 1u) * 4u;
     return h.gbase + (blk << 7) + (slot << 4);
 }
-// the sibling's offset: the next slot of the pair (kBlocks 1: slots 2i, 2i + 1), or the other half's
-// child / the pair 4i + 1, 4i + 2 (kBlocks 2)
-__device__ __forceinline__ uint32_t sib_xor(uint32_t cw) { return kBlocks2 ? ((cw & 1u) ? 48u : 64u) : 16u; }
+// the sibling's offset: the other half's child (slots 0, 4) or the other of the pair 4i + 1, 4i + 2
+__device__ __forceinline__ uint32_t sib_xor(uint32_t cw) { return (cw & 1u) ? 48u : 64u; }
 
 struct Ld {
     double fl;
-    uint32_t cl, kl;
+    uint32_t cl;
     uint4 v;
     bool in;
-    __device__ __forceinline__ void issue(const GHeap& h, int p) { issue_off(h, p, p < h.cap ? kOOR : spill_off(h, p)); }
     // off: the spill offset of p when p >= cap (else ignored)
     __device__ __forceinline__ void issue_off(const GHeap& h, int p, uint32_t off)
     {
@@ -299,7 +244,6 @@ struct Ld {
         v = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(h.spill, in ? kOOR : off, 0, 0));
         fl = h.F[pl];
         cl = h.C[pl];
-        if (kKeys) kl = h.K[pl];
     }
     // the entry (f, code) and its h order key
     template <int HEUR>
@@ -309,19 +253,18 @@ struct Ld {
         const uint64_t b = (uint64_t)__double_as_longlong(fl);
         f = __hiloint2double((int)sel_lanes(m, (uint32_t)(b >> 32), v.y), (int)sel_lanes(m, (uint32_t)b, v.x));
         c = sel_lanes(m, cl, v.z);
-        k = kKeys ? sel_lanes(m, kl, v.w) : hkey<HEUR>(c);
+        k = hkey<HEUR>(c);
     }
 };
-__device__ __forceinline__ void hst_off(const GHeap& h, bool on, int p, uint32_t soff, double f, uint32_t c, uint32_t k,
+__device__ __forceinline__ void hst_off(const GHeap& h, bool on, int p, uint32_t soff, double f, uint32_t c,
                                         int cat = 0)
 {
     if (on && p < h.cap) {
         h.F[p] = f;
         h.C[p] = c;
-        if (kKeys) h.K[p] = k;
     }
     const uint64_t b = (uint64_t)__double_as_longlong(f);
-    const uint4 v = make_uint4((uint32_t)b, (uint32_t)(b >> 32), c, kKeys ? k : 0u);
+    const uint4 v = make_uint4((uint32_t)b, (uint32_t)(b >> 32), c, 0u);
     const uint32_t off = (on && p >= h.cap) ? soff : kOOR;
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned int, v),
                                            h.spill, off, 0, 0);
@@ -329,9 +272,9 @@ __device__ __forceinline__ void hst_off(const GHeap& h, bool on, int p, uint32_t
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned int, v),
                                                h.mirror, off, 0, 0);
 }
-__device__ __forceinline__ void hst(const GHeap& h, bool on, int p, double f, uint32_t c, uint32_t k, int cat = 0)
+__device__ __forceinline__ void hst(const GHeap& h, bool on, int p, double f, uint32_t c, int cat = 0)
 {
-    hst_off(h, on, p, (on && p >= h.cap) ? spill_off(h, p) : kOOR, f, c, k, cat);
+    hst_off(h, on, p, (on && p >= h.cap) ? spill_off(h, p) : kOOR, f, c, cat);
 }
 
 // ---- direction bits (astar2d.hip: bit(p) = !(heap[2p+1] < heap[2p+2]) for nodes with two children,
@@ -485,8 +428,7 @@ __device__ __forceinline__ void pop_leaf(const GHeap& h, const Walk& wk, int n, 
 template <bool T2LDS, int HEUR>
 __device__ __forceinline__ int path_op(const GHeap& h, lmask mon, lmask mpop, uint32_t Q, int Kd, int n, double Xf, uint32_t Xc,
                                        uint32_t Xk, int gl, int gb, double& lastf, uint32_t& lastc, uint32_t& lastk,
-                                       double& rootf, uint32_t& rootc, double& nf, uint32_t& nc, uint32_t& nk, uint32_t cwL,
-                                       lmask mpair = 0ull, double X2f = 0.0, uint32_t X2c = 0u, uint32_t X2k = 0u)
+                                       double& rootf, uint32_t& rootc, double& nf, uint32_t& nc, uint32_t& nk, uint32_t cwL)
 {
     // the lane predicates as lane masks (scalar logic, lm / lb): the step is VALU-issue-bound
     const bool lvl = gl <= Kd;
@@ -496,29 +438,23 @@ __device__ __forceinline__ int path_op(const GHeap& h, lmask mon, lmask mpop, ui
     const lmask mlda = mon & ((mpop & mlvl & kLanesGe1) | (~mpop & lm(gl < Kd)));
     const bool lda = lb(mlda);
     const bool l15 = lb(mon & mpop & kLane15);  // a pop's lane 15: heap[n - 1], the new last
-    const bool p15 = kPair && lb(mpair & kLane15);  // a push pair's lane 15: the second leaf, position n + 1
     const int si = ((q - 1) ^ 1) + 1;
     const lmask mhass = mon & kLanesGe1 & mlvl & lm(si < n);
     const bool hass = lb(mhass);
     double Vf, Sf;
     uint32_t Vc, Sc, Vk, Sk;
-    // kLaneConst: one offset per lane -- lane L's level-L word for the path node q (lane 15 of a pop:
-    // the word of heap[n - 1]'s level, from that level's lane); the sibling is the next slot (^ 16);
+    // one offset per lane -- lane L's level-L word for the path node q (lane 15 of a pop: the word of
+    // heap[n - 1]'s level, from that level's lane); the sibling is the pair's other slot (sib_xor);
     // the stores go to q, at the same offset (every storing lane loaded its q)
     uint32_t offq = kOOR;
     {
         Ld la, ls;
-        if (kLaneConst) {
-            const uint32_t cwK = bp(cwL, gb + (p15 ? Kd : 31 - __clz(n > 0 ? n : 1)));
-            // the offset of q (of n - 1 on a pop's lane 15, which stores nothing; of n + 1, the pair's
-            // second leaf, on a pair's lane 15); only the lanes whose value the operation uses load
-            offq = spill_off_cw(h, (l15 || p15) ? cwK : cwL, l15 ? n - 1 : (p15 ? n + 1 : q));
-            la.issue_off(h, lda ? q : (l15 ? n - 1 : 0), offq);
-            ls.issue_off(h, hass ? si : 0, offq ^ sib_xor(cwL));
-        } else {
-            la.issue(h, lda ? q : (l15 ? n - 1 : 0));
-            ls.issue(h, hass ? si : 0);
-        }
+        const uint32_t cwK = bp(cwL, gb + (31 - __clz(n > 0 ? n : 1)));
+        // the offset of q (of n - 1 on a pop's lane 15, which stores nothing); only the lanes whose
+        // value the operation uses load
+        offq = spill_off_cw(h, l15 ? cwK : cwL, l15 ? n - 1 : q);
+        la.issue_off(h, lda ? q : (l15 ? n - 1 : 0), offq);
+        ls.issue_off(h, hass ? si : 0, offq ^ sib_xor(cwL));
         la.get<HEUR>(Vf, Vc, Vk);
         ls.get<HEUR>(Sf, Sc, Sk);
     }
@@ -531,10 +467,10 @@ __device__ __forceinline__ int path_op(const GHeap& h, lmask mon, lmask mpop, ui
     const bool atb = lb(mbeq), shift = lb((mpop & mblt) | (~mpop & mbgt & mlvl));
     // the levels a pop (<= b) / a push (>= b) rewrites
     const lmask mchg = (mpop & (mblt | mbeq)) | (~mpop & (mbgt | mbeq));
-#if PMP_MQ_BPERM
     // one ds_bpermute per word from lane L +- 1 (the group's own direction) instead of both DPP
-    // shifts and a select: the kernel is VALU-issue-bound, the permutes run on the LDS pipe.  A
-    // shifting lane's source stays in its row (a pop shifts levels < b <= 14, a push levels > b >= 0)
+    // shifts and a select: the kernel is VALU-issue-bound, the permutes run on the LDS pipe (+0.8 %
+    // plans/s over the DPP form, three alternating rounds in tools/r5_call18.sh).  A shifting
+    // lane's source stays in its row (a pop shifts levels < b <= 14, a push levels > b >= 0)
     {
         const int sa = ((int)__lane_id() + (pop ? 1 : -1)) << 2;
         const uint64_t vb = (uint64_t)__double_as_longlong(Vf);
@@ -547,53 +483,11 @@ __device__ __forceinline__ int path_op(const GHeap& h, lmask mon, lmask mpop, ui
         nc = atb ? Xc : (shift ? shc : Vc);
         nk = atb ? Xk : (shift ? shk : Vk);
     }
-#else
-    const double upf = shl1f(Vf), dnf = shr1f(Vf);
-    const uint32_t upc = shl1(Vc), upk = shl1(Vk), dnc = shr1(Vc), dnk = shr1(Vk);
-    nf = atb ? Xf : (shift ? (pop ? upf : dnf) : Vf);
-    nc = atb ? Xc : (shift ? (pop ? upc : dnc) : Vc);
-    nk = atb ? Xk : (shift ? (pop ? upk : dnk) : Vk);
-#endif
-    // ---- a push pair: the second item X2 goes in at position n + 1, the sibling of the first's, so
-    // CPython's _siftdown walks the same ancestors, which now hold the first push's result: X2 lands
-    // at the top of the chain's run of levels greater than it (b2 <= Kd - 1; the chain is ordered),
-    // those levels move down one, and the chain's old bottom (or X2 itself, cnt2 = 0) becomes the
-    // new leaf, which lane 15 holds and stores.  The first leaf stays on lane Kd.
-    int bst = b;  // the first level the operation rewrote
-    lmask mchg2 = mchg;
-    if (kPair && mpair) {
-        const int cnt2 = __popc((uint32_t)((mpair & lm(gl < Kd) & key_lt_m(X2f, X2k, nf, nk)) >> gb) & 0xFFFFu);
-        const int b2 = Kd - cnt2;
-        // lane L takes lane L - 1's chain value (L > b2), lane 15 the chain's bottom (lane Kd - 1);
-        // gl = 0 never shifts (b2 >= 0), so its wrapped source is never used
-        const int src2 = gb + (gl == 15 ? Kd - 1 : gl - 1);
-        const double shf2 = bpf(nf, src2);
-        const uint32_t shc2 = bp(nc, src2), shk2 = bp(nk, src2);
-        const bool at2 = lb(mpair & lm(gl == b2) & lm(gl < Kd)) || (p15 && cnt2 == 0);
-        const bool sh2 = lb(mpair & lm(gl > b2) & lm(gl < Kd)) || (p15 && cnt2 > 0);
-        nf = at2 ? X2f : (sh2 ? shf2 : nf);
-        nc = at2 ? X2c : (sh2 ? shc2 : nc);
-        nk = at2 ? X2k : (sh2 ? shk2 : nk);
-        if (lb(mpair)) bst = b2 < b ? b2 : b;
-        mchg2 = (mchg & ~mpair) | (mpair & lm(gl >= bst));
-    }
-    const bool stq = lb((mon & mchg2 & mlvl) | (kPair ? mpair & kLane15 : 0ull));
-    const int qs = p15 ? n + 1 : q;
-    if (kLaneConst) hst_off(h, stq, qs, offq, nf, nc, nk, pop ? 4 : 2);
-    else hst(h, stq, qs, nf, nc, nk, pop ? 4 : 2);
+    hst_off(h, lb(mon & mchg & mlvl), q, offq, nf, nc, pop ? 4 : 2);
     // the bits of the changed levels' parents: lane L (>= 1) sets its parent's from its new content
     // and its sibling's: bit = !(left < right), an odd position is the left child (choice_bit_k)
     {
-        lmask mbit = mhass & mchg2;
-        if (kPair && mpair) {
-            // a pair's first leaf (lane Kd, a left child) has the second leaf (lane 15) as its sibling
-            const double lf2 = bpf(nf, gb + 15);
-            const uint32_t lk2 = bp(nk, gb + 15);
-            const lmask mkd = mpair & lm(gl == Kd);
-            Sf = lb(mkd) ? lf2 : Sf;
-            Sk = lb(mkd) ? lk2 : Sk;
-            mbit |= mkd;
-        }
+        const lmask mbit = mhass & mchg;
         const bool fe = nf == Sf;
         const lmask lt_ns = lm(nf < Sf) | (lm(fe) & lm(nk < Sk));
         const lmask lt_sn = lm(nf > Sf) | (lm(fe) & lm(nk > Sk));
@@ -608,7 +502,7 @@ __device__ __forceinline__ int path_op(const GHeap& h, lmask mon, lmask mpop, ui
         // heap[n] (level Kd)
         const double r0f = bcf<0>(nf);
         const uint32_t r0c = bc<0>(nc);
-        const int src = gb + ((pop || p15 || (kPair && lb(mpair))) ? 15 : Kd);
+        const int src = gb + (pop ? 15 : Kd);
         const double lf = bpf(pop ? Vf : nf, src);
         const uint32_t lc = bp(pop ? Vc : nc, src), lk = bp(pop ? Vk : nk, src);
         const bool setl = lb(mon & ~(mpop & lm(b == Kd && Q == (uint32_t)n)));
@@ -619,7 +513,7 @@ __device__ __forceinline__ int path_op(const GHeap& h, lmask mon, lmask mpop, ui
         lastk = setl ? lk : lastk;
     }
     wave_sync_mem();
-    return bst;
+    return b;
 }
 
 // THETA: 1 = ThetaStar (theta_star.py:44-108), 2 = LazyThetaStar (lazy_theta_star.py:38-114), with
@@ -652,15 +546,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA ? 3 : 
         const int bits_b = T2LDS ? kBits01 + kT2LBytes : kBits01;
         hp.F = (lds_f64*)(base + bits_b);
         hp.C = (lds_u32*)(base + bits_b + (size_t)8 * lds_cap);
-        hp.K = (lds_u32*)(base + bits_b + (size_t)12 * lds_cap);
         hp.T2 = t2_all + slot * kT2Words;
         hp.spill = __builtin_amdgcn_make_buffer_rsrc(spill_all + (size_t)blockIdx.x * 4u * (size_t)spill_n, 0,
                                                      (int)(4u * (uint32_t)spill_n * 16u), 0x00020000);
-        hp.sbase = (uint32_t)grp * (uint32_t)spill_n * 16u + (uint32_t)(kSpillShift - lds_cap) * 16u;
         hp.gbase = (uint32_t)grp * (uint32_t)spill_n * 16u;
         hp.L0 = 31 - __clz(lds_cap + 1);
-        // kLaneConst: an odd cap (one LDS slot unused), so no sibling pair straddles LDS and spill
-        hp.cap = kLaneConst ? lds_cap - 1 : lds_cap;
+        // an odd cap (one LDS slot unused), so no sibling pair straddles LDS and spill
+        hp.cap = lds_cap - 1;
         if (kMirror & 7)
             hp.mirror = __builtin_amdgcn_make_buffer_rsrc(
                 spill_all + ((size_t)gridDim.x + blockIdx.x) * 4u * (size_t)spill_n, 0,
@@ -683,10 +575,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA ? 3 : 
 
     Walk wk;
     wk.init(gl);
-    const uint32_t cwL = kLaneConst ? lane_cw(hp.L0, gl) : 0u;  // spill-offset word of heap level gl
+    const uint32_t cwL = lane_cw(hp.L0, gl);  // spill-offset word of heap level gl
     // a spilled position p's offset from its level's word (lane gb + level of p)
-    auto soff = [&](int p, bool on) -> uint32_t {
-        if (!kLaneConst) return (on && p >= hp.cap) ? spill_off(hp, p) : kOOR;
+    auto soff = [&](int p) -> uint32_t {
         const uint32_t cw = bp(cwL, gb + (31 - __clz(p + 1)));
         return spill_off_cw(hp, cw, p);
     };
@@ -764,7 +655,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA ? 3 : 
                     lastf = rootf;
                     lastc = rootc;
                     lastk = hkey<HEUR>(rootc);
-                    hst(hp, gl == 0, 0, rootf, rootc, lastk);
+                    hst(hp, gl == 0, 0, rootf, rootc);
                     n = 1;
                     npush = 1;
                     npop = 0;
@@ -816,7 +707,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA ? 3 : 
                 const uint32_t leftk = rank == 0 ? lastk : lkp;
                 bit_set<T2LDS>(hp, lb(lm(inrun) & lm((pos & 1) == 0) & lm(pos > 0)), 30 - __clz(pos + 1),
                                (uint32_t)(pos + 1) >> 1, lb(~key_lt_m(leftf, leftk, ifv, ikk)));
-                hst_off(hp, inrun, pos, soff(pos, inrun), ifv, icm, ikk, 1);
+                hst_off(hp, inrun, pos, soff(pos), ifv, icm, 1);
                 const int top = 31 - __clz(run);
                 lastf = bpf(ifv, gb + top);
                 lastc = bp(icm, gb + top);
@@ -850,12 +741,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA ? 3 : 
         double gpar = 0.0;
         uint32_t ppar = 0u;  // THETA: Pc[pusher] (lane 13)
         Ld pld;
-        // a push pair: the next two pending pushes, the first at an odd position (its sibling next);
-        // heaps of >= 16 entries, so no cached parent (of positions <= n0 + 7) is a new leaf
-        const uint32_t pend2 = pend & (pend - 1u);
-        const lmask Mpair = kPair ? (Mpush & lm(pend2 != 0u) & lm((n & 1) != 0) & lm(n >= 16)) : 0ull;
-        double X2f = 0.0;
-        uint32_t X2c = 0u, X2k = 0u;
         if (push) {
             const int m = __ffs((int)pend) - 1;
             Xf = bpf(ifv, gb + m);
@@ -863,12 +748,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA ? 3 : 
             Xk = bp(ikk, gb + m);
             Q = (uint32_t)n + 1u;
             Kd = 31 - __clz((int)Q);
-            if (kPair) {
-                const int m2 = __ffs((int)pend2) - 1;  // (garbage lanes without a pair never use it)
-                X2f = bpf(ifv, gb + (m2 & 7));
-                X2c = bp(icm, gb + (m2 & 7));
-                X2k = bp(ikk, gb + (m2 & 7));
-            }
         }
         if (pop) {
             // ---- heappop (a_star.py:54), with the 3x3 round and the parent prefetch issued first
@@ -906,14 +785,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA ? 3 : 
         const int pp = (n0 + (gl & 7) - 1) >> 1;  // lanes 0..7: parent of position n0 + lane
         {
             const int pi = lb(Mpop & Mpc & kLanesLt8) ? pp : 0;
-            pld.issue_off(hp, pi, soff(pi, pi >= hp.cap));
+            pld.issue_off(hp, pi, soff(pi));
         }
         const lmask Mop = Mpush | (Mpop & lm(n > 0));
         double nf = 0.0;
         uint32_t nc = 0u, nk = 0u;
         int b = 0;
         b = path_op<T2LDS, HEUR>(hp, Mop, Mpop, Q, Kd, n, Xf, Xc, Xk, gl, gb, lastf, lastc, lastk, rootf, rootc, nf, nc,
-                                 nk, cwL, Mpair, X2f, X2c, X2k);
+                                 nk, cwL);
         {
             double f8;
             uint32_t c8, k8;
@@ -933,12 +812,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA ? 3 : 
             pf8 = onpath ? af : pf8;
             pk8 = onpath ? ak : pk8;
         }
-        {
-            const bool pr = lb(Mpair);
-            pend = push ? (pr ? pend2 & (pend2 - 1u) : pend2) : pend;
-            n += push ? (pr ? 2 : 1) : 0;
-            npush += push ? (pr ? 2 : 1) : 0;
-        }
+        pend = push ? pend & (pend - 1u) : pend;
+        n += push ? 1 : 0;
+        npush += push ? 1 : 0;
 
         // ---- 3. the popped node: 3x3 masks (bit k = cell (x + k/3 - 1, y + k%3 - 1)), CLOSED test,
         //      goal test, getNeighbor (a_star.py:57-82)
@@ -1168,8 +1044,8 @@ int pmp_astar2d_mq_launch(pmp_ctx* ctx, hipStream_t s, int algo, const uint32_t*
         if (lds_cap > heap_cap) lds_cap = (heap_cap + 15) & ~15;
     }
     const int region = bits_b + kEntLds * lds_cap;
-    int spill_n = ((heap_cap > lds_cap ? heap_cap - lds_cap : 1) + kSpillShift + 1) & ~1;
-    if (kBlocks) {  // 16-B units of the group's blocks: bands of two levels from L0 to the deepest level
+    int spill_n;
+    {  // 16-B units of the group's blocks: bands of two levels from L0 to the deepest level
         const int L0 = 31 - __builtin_clz((unsigned)lds_cap + 1u);
         const int Lmax = 31 - __builtin_clz((unsigned)(heap_cap > 1 ? heap_cap : 2));
         const int B = Lmax >= L0 ? (Lmax - L0) / 2 + 1 : 1;

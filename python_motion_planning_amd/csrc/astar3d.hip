@@ -65,11 +65,9 @@ __device__ __forceinline__ bool los3d(const uint32_t* occ, const lds_w32* occl, 
 // LazyThetaStar3D (lazy_theta_star3d.py:41-128).  Theta modes keep any-voxel parents: a per-cell
 // CLOSED parent (cpar) and, per push, the entry's parent in a side table indexed by the push
 // counter (ppar), since an entry's parent may be its pusher's parent.
-#ifndef PMP_A3_WAVES
-#define PMP_A3_WAVES 5  // waves per SIMD the A* / Dijkstra / GBFS variants are compiled for (A/B switch)
-#endif
+constexpr int kA3Waves = 5;  // waves per SIMD the A* / Dijkstra / GBFS variants are compiled for
 template <bool OCC_LDS, int THETA>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA == 0 ? PMP_A3_WAVES : 4))) void astar3d_kernel(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA == 0 ? kA3Waves : 4))) void astar3d_kernel(
     const uint32_t* __restrict__ occ_all, int per_query, int X, int Y, int Z, int heuristic,
     const int32_t* __restrict__ start_xyz, const int32_t* __restrict__ goal_xyz, int nq, double* __restrict__ cost_out,
     int32_t* __restrict__ path_len_out, uint32_t* __restrict__ path_out, int path_cap, int32_t* __restrict__ nexp_out,
@@ -96,7 +94,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA == 0 ?
     heap16::pop_lane_consts(lane, pop_jl, pop_ol);
     const heap16::Walk6 pop_w = heap16::walk6_consts(lane, pop_jl, pop_ol);
     // neighbour lane m < 26: motion m (env3d.py:56-70)
-    const int mdx = lane < 26 ? c_m3[lane][0] : 0, mdy = lane < 26 ? c_m3[lane][1] : 0, mdz = lane < 26 ? c_m3[lane][2] : 0;
+    const int mdx = lane < 26 ? c_m3.m[lane][0] : 0, mdy = lane < 26 ? c_m3.m[lane][1] : 0, mdz = lane < 26 ? c_m3.m[lane][2] : 0;
     const int mchg = (mdx != 0) + (mdy != 0) + (mdz != 0);
     // Planner3D.dist: math.sqrt(1|2|3); GBFS3D pushes every node with g = 0 (gbfs3d.py:78), so its
     // key (h, counter) is this loop's (f, h, counter) with f = 0 + h, and `g >= closed g` is always
@@ -333,11 +331,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA == 0 ?
                     while (!(cx == sx && cy == sy && cz == sz)) {  // goal -> start: cost and length
                         const uint32_t li = ((uint32_t)cx * (uint32_t)Y + (uint32_t)cy) * (uint32_t)Z + (uint32_t)cz;
                         const int d = (int)cdir[li] - 1;
-                        const int chg = (c_m3[d][0] != 0) + (c_m3[d][1] != 0) + (c_m3[d][2] != 0);
+                        const int chg = (c_m3.m[d][0] != 0) + (c_m3.m[d][1] != 0) + (c_m3.m[d][2] != 0);
                         cost += __dsqrt_rn((double)chg);
-                        cx -= c_m3[d][0];
-                        cy -= c_m3[d][1];
-                        cz -= c_m3[d][2];
+                        cx -= c_m3.m[d][0];
+                        cy -= c_m3.m[d][1];
+                        cz -= c_m3.m[d][2];
                         len++;
                     }
                     goal_cost = cost;
@@ -350,9 +348,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA == 0 ?
                             pth[i] = li;
                             if (i == 0) break;
                             const int d = (int)cdir[li] - 1;
-                            cx -= c_m3[d][0];
-                            cy -= c_m3[d][1];
-                            cz -= c_m3[d][2];
+                            cx -= c_m3.m[d][0];
+                            cy -= c_m3.m[d][1];
+                            cz -= c_m3.m[d][2];
                         }
                     }
                 }
@@ -367,10 +365,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA == 0 ?
             item.b = ((((uint32_t)nx & 255u) << 16) | (((uint32_t)ny & 255u) << 8) | ((uint32_t)nz & 255u)) << 5 | (uint32_t)(lane < 26 ? lane : 0);
             qc.set_f(item);
             bool overflow = false;
-#ifndef PMP_A3_BATCH
-#define PMP_A3_BATCH 1
-#endif
-            if (THETA == 0 && PMP_A3_BATCH && vm) {
+            if (THETA == 0 && vm) {
                 // The key is a total order, so the heap's shape is free: the live neighbours are stored
                 // together at n, n + 1, ... (lane order) in one round, and only the ones below their
                 // parent (an entry from before this batch; else assumed below) sift up afterwards, in

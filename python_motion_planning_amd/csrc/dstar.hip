@@ -598,9 +598,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ds
 
 }  // namespace
 
-#ifndef PMP_DSTAR_BUDGET_GIB
-#define PMP_DSTAR_BUDGET_GIB 48
-#endif
 extern "C" int pmp_dstar2d_onpress_batch(pmp_ctx* ctx, void* stream, const uint32_t* occ_bits, int W, int H,
                                          const int32_t* start_xy, const int32_t* goal_xy, int nq, const int32_t* presses,
                                          int npress, double* cost, int32_t* path_len, int32_t* path, int path_cap,
@@ -634,7 +631,7 @@ extern "C" int pmp_dstar2d_onpress_batch(pmp_ctx* ctx, void* stream, const uint3
         return (ncell + 1) * sizeof(DCell) + (size_t)cap * 4 + spill_of(cap) * 16 + 4096 + (npress > 0 ? words * 4 : 0);
     };
     int workers = 256 * per_cu;
-    const size_t budget = (size_t)PMP_DSTAR_BUDGET_GIB << 30;
+    const size_t budget = (size_t)48 << 30;  // per-context scratch of the workers
     const size_t max_workers = budget / per_worker(cap1);
     if ((size_t)workers > max_workers) workers = (int)(max_workers > 0 ? max_workers : 1);
     if (workers > nq) workers = nq;

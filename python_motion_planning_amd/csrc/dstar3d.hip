@@ -22,17 +22,14 @@
 // start == goal: the constructor's map[start] = self.start detaches the goal object from the map
 // (:89-90), so the goal node lives in an extra slot (ncell) that no neighbour scan reaches.
 #include <algorithm>
-#include "heap16.h"
+#include "grid3d.h"
 
 namespace {
 
-constexpr int kMaxDim = 256;
-
-__device__ __constant__ int8_t c_m[26][3] = {
-    {-1, 0, 0}, {-1, 1, 0}, {0, 1, 0}, {1, 1, 0}, {1, 0, 0}, {1, -1, 0}, {0, -1, 0}, {-1, -1, 0},
-    {0, 0, 1}, {0, 0, -1},
-    {-1, 0, 1}, {-1, 1, 1}, {0, 1, 1}, {1, 1, 1}, {1, 0, 1}, {1, -1, 1}, {0, -1, 1}, {-1, -1, 1},
-    {-1, 0, -1}, {-1, 1, -1}, {0, 1, -1}, {1, 1, -1}, {1, 0, -1}, {1, -1, -1}, {0, -1, -1}, {-1, -1, -1}};
+using grid3d::c_m3;
+using grid3d::dist3;
+using grid3d::kMaxDim3;
+using grid3d::lds_w32;
 
 constexpr uint32_t T_NEW = 0, T_OPEN = 1, T_CLOSED = 2;
 
@@ -77,8 +74,6 @@ struct KeyD {
     }
 };
 
-typedef __attribute__((address_space(3))) uint32_t lds_w32;
-
 // The working occupancy of one query (obstacles change in apply_dynamic_obstacles): LDS when it
 // fits, else a per-worker HBM copy.  `p in self.obstacles` is false outside the grid.
 template <bool LDS>
@@ -113,11 +108,6 @@ struct Occ {
         return (ends | ((adj && ch >= 2) ? faces : 0u)) != 0u;
     }
 };
-
-__device__ __forceinline__ double dist3(int dx, int dy, int dz)  // Planner3D.dist
-{
-    return __dsqrt_rn((double)(dx * dx + dy * dy + dz * dz));
-}
 
 struct Geo {
     int X, Y, Z;
@@ -398,9 +388,9 @@ __global__ __launch_bounds__(64) void dstar3d_kernel(
     d.pop_w = heap16::walk6_consts(lane, d.pop_jl, d.pop_ol);
     {
         const int l = lane < 26 ? lane : 0;
-        d.mdx = c_m[l][0];
-        d.mdy = c_m[l][1];
-        d.mdz = c_m[l][2];
+        d.mdx = c_m3.m[l][0];
+        d.mdy = c_m3.m[l][1];
+        d.mdz = c_m3.m[l][2];
         d.mcost = dist3(d.mdx, d.mdy, d.mdz);
     }
     const int R1 = nrounds + 1;
@@ -570,7 +560,7 @@ extern "C" int pmp_dstar3d_batch(pmp_ctx* ctx, void* stream, const uint32_t* occ
                                  int64_t max_process)
 {
     if (!ctx) return PMP_EINVAL;
-    if (X < 1 || Y < 1 || Z < 1 || X > kMaxDim || Y > kMaxDim || Z > kMaxDim)
+    if (X < 1 || Y < 1 || Z < 1 || X > kMaxDim3 || Y > kMaxDim3 || Z > kMaxDim3)
         return pmp_set_err(ctx, PMP_EINVAL, "pmp_dstar3d_batch: X, Y, Z must be in [1, 256]");
     if (nq < 0 || path_cap < 1 || nrounds < 0 || nblk < 0 || (nrounds > 0 && nblk > 0 && !blocks) ||
         (expand && expand_cap < 1))

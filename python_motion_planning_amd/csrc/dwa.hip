@@ -22,11 +22,8 @@
 
 namespace {
 
-#ifndef PMP_DWA_THREADS
-#define PMP_DWA_THREADS 768
-#endif
-constexpr int kThreads = PMP_DWA_THREADS;  // 12 waves per agent (3 per SIMD): <= 168 VGPRs, no scratch spills; 16 waves
-                                           // spill to scratch, 8 hide less latency (tools/dwa_ab.sh)
+constexpr int kThreads = 768;  // 12 waves per agent (3 per SIMD): <= 168 VGPRs, no scratch spills; 16 waves
+                               // spilled to scratch, 8 hid less latency
 constexpr int kMaxN = 4096;    // samples per step held in LDS
 constexpr int kMaxLeaves = 128;
 
@@ -217,15 +214,9 @@ __device__ inline void rollout(const uint32_t* __restrict__ occ, const lds_w32* 
 //    min(sqrt(min d2), R) = R unchanged (dwa.py:164 caps at R), so this superset of the stencil's cells
 //    gives the same obstacle term bit for bit.  A nibble map (four occupancy bits per (fx, fy), built in
 //    LDS per launch) gives the four cells in one LDS read.
-#ifndef PMP_DWA_ROLL_SPLIT
-#define PMP_DWA_ROLL_SPLIT 3  // k-split parts (the rotation table costs a part more than it saves on 512 samples)
-#endif
-#ifndef PMP_DWA_ROLL_LOCAL
-#define PMP_DWA_ROLL_LOCAL 4  // one 1024-thread workgroup per agent
-#endif
-#ifndef PMP_DWA_ROLL_PLAN
-#define PMP_DWA_ROLL_PLAN 3  // dwa_kernel (resolution-sized windows, DWA.plan)
-#endif
+constexpr int kRollSplit = 3;  // k-split parts (the rotation table costs a part more than it saves on 512 samples)
+constexpr int kRollLocal = 4;  // one 1024-thread workgroup per agent
+constexpr int kRollPlan = 3;   // dwa_kernel (resolution-sized windows, DWA.plan)
 
 struct SmallStencil {
     const lds_w32* occ;
@@ -317,13 +308,7 @@ __device__ inline void stencil3(const SmallStencil& T, double x, double y, doubl
 }
 
 // rollout() for R < 2: the same trajectory recurrence and cells
-#ifndef PMP_DWA_PAIR
-#define PMP_DWA_PAIR 1
-#endif
-#ifndef PMP_DWA_COLPAIR
-#define PMP_DWA_COLPAIR 1
-#endif
-template <int SCHEME, bool PAIR = PMP_DWA_PAIR>
+template <int SCHEME, bool PAIR = true>
 __device__ inline void rollout_small(const SmallStencil& T, double dt, int Hh, double x, double y, double sn,
                                      double cs, double sd, double cd, double v, double& xo, double& yo,
                                      double& mind2o)
@@ -654,9 +639,6 @@ constexpr int kSplitChunk = 1024;  // samples of one part held in LDS
 // k = 1 (LOCAL): one 1024-thread workgroup per agent (16 waves, 4 per SIMD at <= 128 VGPRs), all N
 // samples' columns in LDS, no hand-off; the last wave computes the lookahead before its rollouts
 constexpr int kLocalThreads = 1024;
-#ifndef PMP_DWA_LOCAL
-#define PMP_DWA_LOCAL 1  // 0: fixed windows at k = 1 on dwa_kernel (A/B builds)
-#endif
 
 // part p's samples [c[p], c[p + 1]): the host's restatement of the tree's leaves (split_bounds)
 struct DwaSplitBounds {
@@ -887,8 +869,8 @@ __global__ __launch_bounds__(LOCAL ? kLocalThreads : kSplitThreads) void dwa_spl
             st_wt(cols + 2 * kMaxN + c, vel);
         }
     };
-    for (int c = c0 + tid; c < c1; c += (1 + PMP_DWA_COLPAIR) * nt) {
-        const int c2 = PMP_DWA_COLPAIR && c + nt < c1 ? c + nt : c;
+    for (int c = c0 + tid; c < c1; c += 2 * nt) {  // two columns per round
+        const int c2 = c + nt < c1 ? c + nt : c;
         const double w = linsp_at(LW, c % nw), w2 = linsp_at(LW, c2 % nw);
         double th = st[2], th2 = st[2];
         for (int q = 0; q < Hh; q++) {
@@ -896,7 +878,7 @@ __global__ __launch_bounds__(LOCAL ? kLocalThreads : kSplitThreads) void dwa_spl
             th2 = th2 + dt * w2;
         }
         column(c, th);
-        if (PMP_DWA_COLPAIR && c + nt < c1) column(c2, th2);
+        if (c + nt < c1) column(c2, th2);
     }
     DSTAMP(3);
     __syncthreads();
@@ -1099,8 +1081,8 @@ extern "C" int pmp_dwa_step_batch(pmp_ctx* ctx, void* stream, const uint32_t* oc
     PMP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const bool occ_lds = ((size_t)W * H + 31) / 32 <= (size_t)kOccLdsWords;
     const long rot_pairs = dp->nw > 0 ? (long)dp->nw * (long)(int)(dp->predict_time / lp->dt) : -1;
-    const int scheme_split = small_scheme(PMP_DWA_ROLL_SPLIT, W, H, dp->inflation, occ_lds, rot_pairs);
-    const int scheme_local = small_scheme(PMP_DWA_ROLL_LOCAL, W, H, dp->inflation, occ_lds, rot_pairs);
+    const int scheme_split = small_scheme(kRollSplit, W, H, dp->inflation, occ_lds, rot_pairs);
+    const int scheme_local = small_scheme(kRollLocal, W, H, dp->inflation, occ_lds, rot_pairs);
     // parts per agent: auto (dwa_split 0) = the CUs over the agents, at most 16; 1 = one workgroup per
     // agent.  Only windows of fixed size (nv, nw > 0) split, into leaf-aligned parts of <= kSplitChunk.
     int k = 1;
@@ -1147,7 +1129,7 @@ extern "C" int pmp_dwa_step_batch(pmp_ctx* ctx, void* stream, const uint32_t* oc
         PMP_HIP_CHECK(ctx, hipGetLastError());
         return PMP_OK;
     }
-    if (PMP_DWA_LOCAL && fixed) {
+    if (fixed) {
         // one workgroup per agent, one launch per plan iteration (the k-split kernel at k = 1: no scratch,
         // no hand-off)
         DwaSplitScratch X = {nullptr, nullptr, nullptr};
@@ -1166,7 +1148,7 @@ extern "C" int pmp_dwa_step_batch(pmp_ctx* ctx, void* stream, const uint32_t* oc
         PMP_HIP_CHECK(ctx, hipGetLastError());
         return PMP_OK;
     }
-    const int scheme_plan = small_scheme(PMP_DWA_ROLL_PLAN, W, H, dp->inflation, occ_lds) == 3 ? 3 : 0;
+    const int scheme_plan = small_scheme(kRollPlan, W, H, dp->inflation, occ_lds) == 3 ? 3 : 0;
     auto kern = scheme_plan == 3 ? dwa_kernel<true, 3> : occ_lds ? dwa_kernel<true, 0> : dwa_kernel<false, 0>;
     hipLaunchKernelGGL(kern, dim3(na), dim3(kThreads), sizeof(DwaShared), (hipStream_t)stream, occ_bits, ox, oy, W,
                        H, *lp, *dp, na, state, goal, path_xy, path_off, iters, u, best, status, n_steps, hist_pose, eval,

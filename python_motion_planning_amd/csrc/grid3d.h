@@ -1,7 +1,10 @@
-// Grid helpers shared by the one-wave-per-query 3D graph-search kernels (astar3d.hip, jps3d.hip):
-// Grid3D's 26 motions, the (f, h, counter) heap key, the occupancy bit of a voxel (from HBM or from
-// the bitmap staged in LDS), Planner3D.dist and the per-context scratch budget.  The longest-first
-// pre-pass both launchers use is pmp_lpt_order3d (pmp_internal.h, defined in astar3d.hip).
+// Grid helpers shared by the one-wave-per-query 3D kernels.  All four planners (astar3d.hip,
+// jps3d.hip, dstar3d.hip, lpa3d.hip) take Grid3D's 26 motions, Planner3D.dist, the dimension limit
+// and the LDS word type from here; astar3d.hip and jps3d.hip also the (f, h, counter) heap key, the
+// occupancy bit of a voxel (from HBM or from the bitmap staged in LDS), the LDS occupancy threshold
+// and the per-context scratch budget (dstar3d.hip and lpa3d.hip keep their own occupancy structs,
+// threshold and budget).  The longest-first pre-pass the launchers use is pmp_lpt_order3d
+// (pmp_internal.h, defined in astar3d.hip).
 #pragma once
 #include "heap16.h"
 
@@ -9,12 +12,17 @@ namespace grid3d {
 
 constexpr int kMaxDim3 = 256;
 
-// Grid3D.motions (env3d.py:56-70), in the reference's order
-static __device__ __constant__ int8_t c_m3[26][3] = {
+// Grid3D.motions (env3d.py:56-70), in the reference's order: kM3 for compile-time use (indexed by
+// unrolled loop counters), c_m3 the same table in constant memory (indexed by a lane's motion)
+struct Motions3 {
+    int8_t m[26][3];
+};
+constexpr Motions3 kM3 = {{
     {-1, 0, 0}, {-1, 1, 0}, {0, 1, 0}, {1, 1, 0}, {1, 0, 0}, {1, -1, 0}, {0, -1, 0}, {-1, -1, 0},
     {0, 0, 1}, {0, 0, -1},
     {-1, 0, 1}, {-1, 1, 1}, {0, 1, 1}, {1, 1, 1}, {1, 0, 1}, {1, -1, 1}, {0, -1, 1}, {-1, -1, 1},
-    {-1, 0, -1}, {-1, 1, -1}, {0, 1, -1}, {1, 1, -1}, {1, 0, -1}, {1, -1, -1}, {0, -1, -1}, {-1, -1, -1}};
+    {-1, 0, -1}, {-1, 1, -1}, {0, 1, -1}, {1, 1, -1}, {1, 0, -1}, {1, -1, -1}, {0, -1, -1}, {-1, -1, -1}}};
+alignas(16) static __device__ __constant__ Motions3 c_m3 = kM3;  // aligned like an array of its size
 
 using heap16::Ent;  // g = path cost, a = push counter, b = cm; derived f = g + h, hk = h order key
 
@@ -71,9 +79,8 @@ __device__ __forceinline__ double dist3(int dx, int dy, int dz)  // Planner3D.di
 }
 
 // per-context scratch budget of the 3D planners (heap spill + closed state + any-voxel parents per worker)
-#ifndef PMP_ASTAR3D_BUDGET_GIB
-#define PMP_ASTAR3D_BUDGET_GIB 48  // 32: ~4,870 workers at C5 (2.05 M plans/s), 48: the 20-per-CU 5,120 (2.09-2.11 M, tools/calls/r6_call53.sh)
-#endif
-constexpr size_t kScratchBudget3 = (size_t)PMP_ASTAR3D_BUDGET_GIB << 30;
+// 48 GiB: the 20-per-CU 5,120 workers at C5 (2.09-2.11 M plans/s); 32 GiB fitted ~4,870 (2.05 M,
+// tools/calls/r6_call53.sh)
+constexpr size_t kScratchBudget3 = (size_t)48 << 30;
 
 }  // namespace grid3d

@@ -282,7 +282,7 @@ __global__ __launch_bounds__(64) void jps3d_kernel(
             bool has = false;
             int jx = x, jy = y, jz = z;
             for (int m = 0; m < 26; m++) {
-                const V3 d{c_m3[m][0], c_m3[m][1], c_m3[m][2]};
+                const V3 d{c_m3.m[m][0], c_m3.m[m][1], c_m3.m[m][2]};
                 const int nz = (d.x != 0) + (d.y != 0) + (d.z != 0);
                 int found = 0;  // the hit's step number, 0 = None
                 for (int base = 0;; base += 64) {

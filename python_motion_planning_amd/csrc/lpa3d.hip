@@ -24,42 +24,21 @@
 // apply_change then expands nothing.
 #include <algorithm>
 #include "pmp_internal.h"
+#include "grid3d.h"
 
 namespace {
 
-constexpr int kMaxDim = 256;
-// Write-traffic attribution (dev builds, tools/build_variant.sh): every store of the selected
-// categories is issued twice, the copy into a mirror of the worker's arrays, so the extra WRITE_SIZE
-// over the plain build is that category's traffic.  Bits: 1 U's spilled positions (shifts, pushes),
-// 2 the g / rhs values, 4 the written-this-query bits (ORs and the per-query clear).
-#ifndef PMP_L3_MIRROR
-#define PMP_L3_MIRROR 0
-#endif
-constexpr int kL3Mirror = PMP_L3_MIRROR;
+using grid3d::c_m3;
+using grid3d::dist3;
+using grid3d::kM3;  // the motions as a compile-time constant (indexed only by unrolled loop counters)
+using grid3d::kMaxDim3;
+using grid3d::lds_w32;
 // Deferred removes (round 6): U.remove inside one expansion's block leaves a hole instead of shifting
 // the tail; positions stay logical (the reference's list indices) and map to the physical array
-// through the pending holes; the block's end closes every hole in one compaction pass.  0: the
-// round-5 form (every remove shifts the tail at once).
-#ifndef PMP_L3_DEFER
-#define PMP_L3_DEFER 1
-#endif
-constexpr bool kDefer = PMP_L3_DEFER != 0;
+// through the pending holes; the block's end closes every hole in one compaction pass.  (The
+// round-5 form shifted the tail at every remove.)
 constexpr double kInf = __builtin_huge_val();
 
-__device__ __constant__ int8_t c_m[26][3] = {
-    {-1, 0, 0}, {-1, 1, 0}, {0, 1, 0}, {1, 1, 0}, {1, 0, 0}, {1, -1, 0}, {0, -1, 0}, {-1, -1, 0},
-    {0, 0, 1}, {0, 0, -1},
-    {-1, 0, 1}, {-1, 1, 1}, {0, 1, 1}, {1, 1, 1}, {1, 0, 1}, {1, -1, 1}, {0, -1, 1}, {-1, -1, 1},
-    {-1, 0, -1}, {-1, 1, -1}, {0, 1, -1}, {1, 1, -1}, {1, 0, -1}, {1, -1, -1}, {0, -1, -1}, {-1, -1, -1}};
-
-// the same table as a compile-time constant (indexed only by unrolled loop counters)
-constexpr int8_t kM[26][3] = {
-    {-1, 0, 0}, {-1, 1, 0}, {0, 1, 0}, {1, 1, 0}, {1, 0, 0}, {1, -1, 0}, {0, -1, 0}, {-1, -1, 0},
-    {0, 0, 1}, {0, 0, -1},
-    {-1, 0, 1}, {-1, 1, 1}, {0, 1, 1}, {1, 1, 1}, {1, 0, 1}, {1, -1, 1}, {0, -1, 1}, {-1, -1, 1},
-    {-1, 0, -1}, {-1, 1, -1}, {0, 1, -1}, {1, 1, -1}, {1, 0, -1}, {1, -1, -1}, {0, -1, -1}, {-1, -1, -1}};
-
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef __attribute__((address_space(3))) int32_t lds_i32;
 typedef __attribute__((address_space(3))) double lds_f64;
 
@@ -108,7 +87,7 @@ struct Mask125 {
 // working occupancy (apply_change edits it): LDS when it fits, else the worker's HBM copy;
 // `p in self.obstacles` is false outside the grid
 struct Occ {
-    lds_u32* l;
+    lds_w32* l;
     uint32_t* g;
     bool lds;
     Geo geo;
@@ -135,11 +114,6 @@ struct Occ {
     }
 };
 
-__device__ __forceinline__ double dist_unit(int dx, int dy, int dz)  // Planner3D.dist of a motion
-{
-    return __dsqrt_rn((double)(dx * dx + dy * dy + dz * dz));
-}
-
 // U: positions < cap in LDS, the rest in the worker's HBM arrays
 struct UList {
     lds_i32* lc;
@@ -148,9 +122,6 @@ struct UList {
     int32_t* gc;
     double* g1;
     double* g2;
-    int32_t* mgc;  // kL3Mirror & 1: the mirror of the spilled part
-    double* mg1;
-    double* mg2;
     int cap;
     int n;
     // SP = false: every position touched is < cap (pure LDS code, no vector-memory waits)
@@ -178,11 +149,6 @@ struct UList {
             gc[k - cap] = c;
             g1[k - cap] = a;
             g2[k - cap] = b;
-            if (kL3Mirror & 1) {
-                mgc[k - cap] = c;
-                mg1[k - cap] = a;
-                mg2[k - cap] = b;
-            }
         }
     }
 };
@@ -208,14 +174,10 @@ struct L3 {
     // U's share spilled more lists to HBM -- +50 % writes, -9 % plans/s.)
     uint32_t* gt;
     uint32_t* rt;
-    double* mg;     // kL3Mirror & 2: mirrors of g / rhs
-    double* mrhs;
-    uint32_t* mgt;  // kL3Mirror & 4: mirrors of the bits
-    uint32_t* mrt;
     bool touch;
     lds_f64* cube;  // 125 g values of the 5x5x5 block around the centre
     int lane;
-    // kDefer: the holes pending in U's physical array (wave-uniform count hm <= 28 -- the popped node
+    // the holes pending in U's physical array (wave-uniform count hm <= 28 -- the popped node
     // and the 27 block voxels; lane j < hm holds hole j's boundary b_j = the live entries before it).
     // Logical position L sits at physical L + #{j : b_j <= L}.
     int hb;
@@ -244,8 +206,6 @@ struct L3 {
     __device__ __forceinline__ void mark(uint32_t* t, int c) const
     {
         if (touch) __hip_atomic_fetch_or(t + (c >> 5), 1u << (c & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((kL3Mirror & 4) && touch)
-            __hip_atomic_fetch_or((t == gt ? mgt : mrt) + (c >> 5), 1u << (c & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 
     __device__ __forceinline__ double hval(int x, int y, int z) const
@@ -254,47 +214,17 @@ struct L3 {
         return heur == 1 ? (double)(dx + dy + dz) : __dsqrt_rn((double)(dx * dx + dy * dy + dz * dz));
     }
 
-    // U.remove(U[i]): the tail moves left one slot; 4 elements per lane per round (all loads of a
-    // round before its stores; a round never reads what an earlier round wrote)
-    template <bool SP>
-    __device__ __forceinline__ void remove_at_t(int i)
-    {
-        // the loads of a round are unconditional (clamped to the last element) so they issue back to
-        // back with one wait; only the stores are masked
-        const int last = U.n - 1;
-        for (int base = i; base < last; base += 256) {
-            int32_t c[4];
-            double a[4], b[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int k = base + lane + 64 * j;
-                U.template ld<SP>(k < last ? k + 1 : last, c[j], a[j], b[j]);
-            }
-            wsync();
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int k = base + lane + 64 * j;
-                if (k < last) U.template st<SP>(k, c[j], a[j], b[j]);
-            }
-            wsync();
-        }
-    }
+    // U.remove(U[i]): a hole at logical i; later holes' boundaries past i drop by one
     __device__ __forceinline__ void remove_at(int i, Track& t)
     {
-        if (kDefer) {  // a hole at logical i: later holes' boundaries past i drop by one
-            if (lane < hm && hb > i) hb -= 1;
-            if (lane == hm) hb = i;
-            hm += 1;
-        } else if (U.n <= U.cap) {
-            remove_at_t<false>(i);
-        } else {
-            remove_at_t<true>(i);
-        }
+        if (lane < hm && hb > i) hb -= 1;
+        if (lane == hm) hb = i;
+        hm += 1;
         U.n -= 1;
         if (t.pos == i) t.pos = -1;
         else if (t.pos > i) t.pos -= 1;
     }
-    // physical index of logical position L (kDefer)
+    // physical index of logical position L
     __device__ __forceinline__ int phys(int L) const
     {
         int P = L;
@@ -334,7 +264,7 @@ struct L3 {
     }
     __device__ __forceinline__ void compact()
     {
-        if (!kDefer || hm == 0) return;
+        if (hm == 0) return;
         int from = U.n;
         for (int j = 0; j < hm; j++) from = min(from, __builtin_amdgcn_readlane(hb, j));
         if (U.n + hm <= U.cap) compact_t<false>(from);
@@ -344,26 +274,21 @@ struct L3 {
 
     // heapq.heappush(U, node): lane j (1..D) loads ancestor j of position n; the ancestors that move
     // down are the run of "new < ancestor" from the parent up (_siftdown stops at the first one that
-    // is not greater).  `me` = this lane tracks the pushed voxel.  kDefer: lane j (0..D) maps path
+    // is not greater).  `me` = this lane tracks the pushed voxel.  Lane j (0..D) maps path
     // position (np1 >> j) - 1 to its physical index first.
     template <bool SP>
     __device__ __forceinline__ int push_t(int32_t c, double k1, double k2, uint32_t np1, int& s)
     {
         const int D = 31 - __clz((int)np1);
         const bool on = lane >= 1 && lane <= D;
-        const int aj = on ? (int)(np1 >> lane) - 1 : 0;
-        // kDefer: lane j's path position and the one below it (its store target), both mapped
-        int pj = aj, pdown = 0;
-        if (kDefer) {
-            const int L0 = lane <= D ? (int)(np1 >> lane) - 1 : 0;
-            const int L1 = on ? (int)(np1 >> (lane - 1)) - 1 : 0;
-            pj = L0;
-            pdown = L1;
-            for (int h = 0; h < hm; h++) {
-                const int bh = __builtin_amdgcn_readlane(hb, h);
-                pj += L0 >= bh ? 1 : 0;
-                pdown += L1 >= bh ? 1 : 0;
-            }
+        // lane j's path position and the one below it (its store target), both mapped
+        const int L0 = lane <= D ? (int)(np1 >> lane) - 1 : 0;
+        const int L1 = on ? (int)(np1 >> (lane - 1)) - 1 : 0;
+        int pj = L0, pdown = L1;
+        for (int h = 0; h < hm; h++) {
+            const int bh = __builtin_amdgcn_readlane(hb, h);
+            pj += L0 >= bh ? 1 : 0;
+            pdown += L1 >= bh ? 1 : 0;
         }
         int32_t ac = 0;
         double a1 = 0.0, a2 = 0.0;
@@ -371,14 +296,9 @@ struct L3 {
         const uint64_t lt = ballot(on && key_lt(k1, k2, a1, a2));
         s = __builtin_ctzll(~(lt >> 1));  // trailing ones from lane 1
         wsync();
-        if (kDefer) {
-            if (on && lane <= s) U.template st<SP>(pdown, ac, a1, a2);
-            const int pdst = __builtin_amdgcn_readlane(pj, s);
-            if (lane == 0) U.template st<SP>(pdst, c, k1, k2);
-        } else {
-            if (on && lane <= s) U.template st<SP>((int)(np1 >> (lane - 1)) - 1, ac, a1, a2);
-            if (lane == 0) U.template st<SP>((int)(np1 >> s) - 1, c, k1, k2);
-        }
+        if (on && lane <= s) U.template st<SP>(pdown, ac, a1, a2);
+        const int pdst = __builtin_amdgcn_readlane(pj, s);
+        if (lane == 0) U.template st<SP>(pdst, c, k1, k2);
         wsync();
         return (int)(np1 >> s) - 1;
     }
@@ -386,7 +306,7 @@ struct L3 {
     {
         const uint32_t np1 = (uint32_t)U.n + 1u;
         int s;
-        const int dst = U.n + (kDefer ? hm : 0) < U.cap ? push_t<false>(c, k1, k2, np1, s) : push_t<true>(c, k1, k2, np1, s);
+        const int dst = U.n + hm < U.cap ? push_t<false>(c, k1, k2, np1, s) : push_t<true>(c, k1, k2, np1, s);
         // tracked positions: ancestor j (1..s) -> ancestor j-1
         if (t.pos >= 0) {
             const int p1 = t.pos + 1;
@@ -429,7 +349,7 @@ struct L3 {
             gin1 = gin1 && gw(i1);
         }
         const int m = lane < 26 ? lane : 0;
-        const int dx = lane < 26 ? c_m[m][0] : 0, dy = lane < 26 ? c_m[m][1] : 0, dz = lane < 26 ? c_m[m][2] : 0;
+        const int dx = lane < 26 ? c_m3.m[m][0] : 0, dy = lane < 26 ? c_m3.m[m][1] : 0, dz = lane < 26 ? c_m3.m[m][2] : 0;
         const int px = cx + dx, py = cy + dy, pz = cz + dz;
         const bool mine = lane <= 26 && geo.in(px, py, pz);
         const int P = mine ? geo.id(px, py, pz) : 0;
@@ -483,7 +403,7 @@ struct L3 {
             bool any = false;
 #pragma unroll
             for (int u = 0; u < 26; u++) {
-                const int ex = kM[u][0], ey = kM[u][1], ez = kM[u][2];  // compile-time after unrolling
+                const int ex = kM3.m[u][0], ey = kM3.m[u][1], ez = kM3.m[u][2];  // compile-time after unrolling
                 const int qx = ax + ex, qy = ay + ey, qz = az + ez;
                 const int qb = (qx * 5 + qy) * 5 + qz;
                 if (!inm.at(qb) || obm.at(qb)) continue;  // getNeighbor: in the map, endpoint free
@@ -511,10 +431,10 @@ struct L3 {
         // ---- U positions of the 27 voxels: one scan
         Track t;
         t.pos = -1;
-        // kDefer: at most one hole here (the popped node's, expand); the scan walks the physical
-        // array, skips the hole and reports logical positions
-        const int hole = (kDefer && hm) ? __builtin_amdgcn_readlane(hb, 0) : 0x7fffffff;
-        const int nph = U.n + (kDefer ? hm : 0);
+        // at most one hole here (the popped node's, expand); the scan walks the physical array, skips
+        // the hole and reports logical positions
+        const int hole = hm ? __builtin_amdgcn_readlane(hb, 0) : 0x7fffffff;
+        const int nph = U.n + hm;
         const bool usp = nph > U.cap;
         for (int base = 0; base < nph; base += 64) {
             const int k = base + lane;
@@ -582,12 +502,10 @@ struct L3 {
             const bool upd = mine && P != start && (is_nb || (lane == 26 && do_center)) && rv != rvl;
             if (upd) {
                 rhs[P] = rv;
-                if (kL3Mirror & 2) mrhs[P] = rv;
                 mark(rt, P);
             }
             if (expand && lane == 0) {
                 g[center] = gnew;
-                if (kL3Mirror & 2) mg[center] = gnew;
                 mark(gt, center);
             }
         }
@@ -606,11 +524,6 @@ struct L3 {
     }
 };
 
-__host__ __device__ inline size_t l3_mirror_bytes(size_t ncell, int words)
-{
-    return ((2 * ncell + 2 * (ncell + 1)) * 8 + (ncell + 1) * 4 + (size_t)words * 8 + 255) & ~(size_t)255;
-}
-
 __global__ __launch_bounds__(64) void lpa3d_kernel(
     const uint32_t* __restrict__ occ_all, int per_query, int X, int Y, int Z, int heur,
     const int32_t* __restrict__ start_xyz, const int32_t* __restrict__ goal_xyz, int nq,
@@ -618,7 +531,7 @@ __global__ __launch_bounds__(64) void lpa3d_kernel(
     int32_t* __restrict__ path_out, int path_cap, int64_t* __restrict__ nexp_out, int32_t* __restrict__ status_out,
     int64_t* __restrict__ counters, int64_t max_exp, int* __restrict__ queue, double* __restrict__ scr_f64,
     int32_t* __restrict__ scr_i32, uint32_t* __restrict__ occ_scr, int words, int occ_lds, int ucap,
-    const int32_t* __restrict__ order, int prio_n, uint32_t* __restrict__ bits_all, unsigned char* __restrict__ mirror)
+    const int32_t* __restrict__ order, int prio_n, uint32_t* __restrict__ bits_all)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = lane_id();
@@ -633,7 +546,7 @@ __global__ __launch_bounds__(64) void lpa3d_kernel(
     S.U.l2 = (lds_f64*)(smem + 1024 + (size_t)8 * ucap);
     S.U.lc = (lds_i32*)(smem + 1024 + (size_t)16 * ucap);
     S.U.cap = ucap;
-    S.occ.l = (lds_u32*)(smem + 1024 + (size_t)20 * ucap);
+    S.occ.l = (lds_w32*)(smem + 1024 + (size_t)20 * ucap);
     S.occ.lds = occ_lds != 0;
     S.touch = true;
     S.hb = 0;
@@ -650,16 +563,6 @@ __global__ __launch_bounds__(64) void lpa3d_kernel(
         S.U.g1 = f + 2 * (size_t)ncell;
         S.U.g2 = S.U.g1 + spill;
         S.U.gc = scr_i32 + (size_t)blockIdx.x * spill;
-        if (kL3Mirror) {  // the mirror: g, rhs, U keys, U cells, the two bit arrays
-            double* mf = (double*)(mirror + (size_t)blockIdx.x * l3_mirror_bytes(ncell, words));
-            S.mg = mf;
-            S.mrhs = mf + ncell;
-            S.U.mg1 = mf + 2 * (size_t)ncell;
-            S.U.mg2 = S.U.mg1 + spill;
-            S.U.mgc = (int32_t*)(S.U.mg2 + spill);
-            S.mgt = (uint32_t*)(S.U.mgc + spill);
-            S.mrt = S.mgt + words;
-        }
     }
     const int R1 = nr + 1;
 
@@ -717,15 +620,10 @@ __global__ __launch_bounds__(64) void lpa3d_kernel(
                 for (int w = lane; w < words; w += 64) {
                     __hip_atomic_store(S.gt + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(S.rt + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (kL3Mirror & 4) {
-                        __hip_atomic_store(S.mgt + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(S.mrt + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
                 }
                 wsync();
                 if (lane == 0) {
                     S.rhs[S.start] = 0.0;
-                    if (kL3Mirror & 2) S.mrhs[S.start] = 0.0;
                     S.mark(S.rt, S.start);
                 }
             } else {
@@ -860,7 +758,7 @@ __global__ __launch_bounds__(64) void lpa3d_kernel(
                     int x, y, z;
                     S.geo.xyz(node, x, y, z);
                     const int m = lane < 26 ? lane : 0;
-                    const int nx = x + c_m[m][0], ny = y + c_m[m][1], nz = z + c_m[m][2];
+                    const int nx = x + c_m3.m[m][0], ny = y + c_m3.m[m][1], nz = z + c_m3.m[m][2];
                     bool ok = lane < 26 && S.geo.in(nx, ny, nz) && !S.occ.at(nx, ny, nz) &&
                               !S.occ.coll(x, y, z, nx, ny, nz);
                     double gn = kInf;
@@ -875,8 +773,8 @@ __global__ __launch_bounds__(64) void lpa3d_kernel(
                         const double gk = rl_f64(gn, k);
                         if (bm < 0 || gk < bg) { bm = k; bg = gk; }
                     }
-                    cost += dist_unit(c_m[bm][0], c_m[bm][1], c_m[bm][2]);
-                    node = S.geo.id(x + c_m[bm][0], y + c_m[bm][1], z + c_m[bm][2]);
+                    cost += dist3(c_m3.m[bm][0], c_m3.m[bm][1], c_m3.m[bm][2]);
+                    node = S.geo.id(x + c_m3.m[bm][0], y + c_m3.m[bm][1], z + c_m3.m[bm][2]);
                     if (lane == 0 && len < path_cap) pth[len] = node;
                     len++;
                     if (++safety >= 100000) { st = PMP_NO_PATH; break; }
@@ -898,7 +796,7 @@ __global__ __launch_bounds__(64) void lpa3d_kernel(
                     // safety + 1 .. 99999 + 1, take them in turn
                     const int mi = __builtin_amdgcn_ds_bpermute(((safety - lam + 1 + lane) & 63) << 2, ring);
                     const int mm = lane < lam ? mi : 0;
-                    const double dc = dist_unit(c_m[mm][0], c_m[mm][1], c_m[mm][2]);
+                    const double dc = dist3(c_m3.m[mm][0], c_m3.m[mm][1], c_m3.m[mm][2]);
                     int i = 0;
                     for (int j = safety; j < 100000; j++) {
                         cost += rl_f64(dc, i);
@@ -955,7 +853,7 @@ extern "C" int pmp_lpastar3d_batch(pmp_ctx* ctx, void* stream, const uint32_t* o
                                    int64_t max_expansions)
 {
     if (!ctx) return PMP_EINVAL;
-    if (X < 1 || Y < 1 || Z < 1 || X > kMaxDim || Y > kMaxDim || Z > kMaxDim)
+    if (X < 1 || Y < 1 || Z < 1 || X > kMaxDim3 || Y > kMaxDim3 || Z > kMaxDim3)
         return pmp_set_err(ctx, PMP_EINVAL, "pmp_lpastar3d_batch: X, Y, Z must be in [1, 256]");
     if (heuristic != 0 && heuristic != 1) return pmp_set_err(ctx, PMP_EINVAL, "pmp_lpastar3d_batch: heuristic must be 0 or 1");
     if (nq < 0 || path_cap < 1 || nr < 0 || (nr > 0 && !changes))
@@ -995,15 +893,10 @@ extern "C" int pmp_lpastar3d_batch(pmp_ctx* ctx, void* stream, const uint32_t* o
         const int rc = pmp_lpt_order3d(ctx, s, start_xyz, goal_xyz, nq, X, Y, Z, workers, &order);
         if (rc) return rc;
     }
-    unsigned char* mirror = nullptr;
-    if (kL3Mirror) {
-        mirror = (unsigned char*)pmp_scratch(ctx, SCR_MQ_PC, (size_t)workers * l3_mirror_bytes(ncell, words));
-        if (!mirror) return PMP_ENOMEM;
-    }
     hipLaunchKernelGGL(lpa3d_kernel, dim3(workers), dim3(64), lds, s, occ_bits, per_query, X, Y, Z, heuristic, start_xyz,
                        goal_xyz, nq, changes, nr, cost, path_len, path, path_cap, n_expanded, status, counters,
                        max_expansions, queue, f, i32, occw, words, occ_lds ? 1 : 0, ucap, (const int32_t*)order,
-                       order ? ctx->astar_prio_n : 0, (uint32_t*)(i32 + (size_t)workers * spill), mirror);
+                       order ? ctx->astar_prio_n : 0, (uint32_t*)(i32 + (size_t)workers * spill));
     PMP_HIP_CHECK(ctx, hipGetLastError());
     return PMP_OK;
 }

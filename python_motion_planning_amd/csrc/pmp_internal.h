@@ -143,13 +143,8 @@ __device__ __forceinline__ bool lb(lmask m) { return __builtin_amdgcn_inverse_ba
 // cells: a tile is one 128-B line, so the 3x3 round of an expansion touches ~1.4 lines on average
 // instead of one per grid row x-1, x, x+1 (the row-major layout, x * H + y), and an A* front's
 // cells share lines in both directions.  tH = tiles along y.
-#ifndef PMP_CST_TX
-#define PMP_CST_TX 3  // log2 tile width along x
-#endif
-#ifndef PMP_CST_TY
-#define PMP_CST_TY 4  // log2 tile height along y
-#endif
-constexpr int kCstTx = PMP_CST_TX, kCstTy = PMP_CST_TY;
+constexpr int kCstTx = 3;  // log2 tile width along x
+constexpr int kCstTy = 4;  // log2 tile height along y
 __host__ __device__ inline size_t cst_tiled_bytes(int W, int H)
 {
     return (size_t)((W + (1 << kCstTx) - 1) >> kCstTx) * (size_t)((H + (1 << kCstTy) - 1) >> kCstTy) *
@@ -166,13 +161,8 @@ __device__ __forceinline__ uint32_t cst_idx(int x, int y, uint32_t tH)
 // pusher's G (read at every pop) and the node's (written at its expansion) are neighbours, in one line
 // for most motions (the row-major layout puts every x +- 1 neighbour in another line).  The slot stride
 // (cells) covers the padded tiles; the single-query engine keeps row-major G inside the same stride.
-#ifndef PMP_G_TX
-#define PMP_G_TX 2  // log2 tile width along x
-#endif
-#ifndef PMP_G_TY
-#define PMP_G_TY 2  // log2 tile height along y
-#endif
-constexpr int kGTx = PMP_G_TX, kGTy = PMP_G_TY;
+constexpr int kGTx = 2;  // log2 tile width along x
+constexpr int kGTy = 2;  // log2 tile height along y
 __host__ __device__ inline size_t g_slot_cells(int W, int H)
 {
     return (size_t)((W + (1 << kGTx) - 1) >> kGTx) * (size_t)((H + (1 << kGTy) - 1) >> kGTy) * ((size_t)1 << (kGTx + kGTy));

@@ -27,35 +27,18 @@ namespace {
 // chain of barriers and dependent L2 rounds, so a second query per CU hides it -- 955 -> 1,475 plans/s
 // over 512 x 1; 128 x 4 and a 168-VGPR 256 x 3 build are slower.  Round 5, when the whole-tree f32 scans
 // dominated, 512 x 1 was the faster shape)
-#ifndef PMP_RRT_NT
-#define PMP_RRT_NT 256
-#endif
-constexpr int kNT = PMP_RRT_NT;
-#ifndef PMP_RRT_PERCU
-#define PMP_RRT_PERCU (512 / PMP_RRT_NT)
-#endif
-#ifndef PMP_RRT_MINW
-#define PMP_RRT_MINW 1
-#endif
+constexpr int kNT = 256;
+constexpr int kPerCu = 512 / kNT;  // workgroups per CU at least
 constexpr int kWaves = kNT / 64;
 constexpr int kMaxObs = 256;   // per obstacle kind
 constexpr int kMaxBnd = 8;
 // The candidate lists keep their first entries in LDS and the rest in per-query HBM lists (C3: an
 // r = 10 ball holds tens of nodes), so the LDS goes to the coarse tree copy.
-#ifndef PMP_RRT_KMAX
-#define PMP_RRT_KMAX 128
-#endif
-constexpr int kMaxA = PMP_RRT_KMAX;  // collision-free improving candidates per iteration
-constexpr int kMaxT = PMP_RRT_KMAX;  // candidates awaiting a collision test per phase
-constexpr int kMaxK = PMP_RRT_KMAX;  // in-radius candidates kept in LDS (more spill to the HBM list)
-#ifndef PMP_RRT_RND
-#define PMP_RRT_RND 256
-#endif
-#ifndef PMP_RRT_MAXH
-#define PMP_RRT_MAXH 512
-#endif
-constexpr int kRnd = PMP_RRT_RND;    // random doubles staged in LDS
-constexpr int kMaxH = PMP_RRT_MAXH;  // coarse in-radius hits staged in LDS (more are resolved inline)
+constexpr int kMaxA = 128;  // collision-free improving candidates per iteration
+constexpr int kMaxT = 128;  // candidates awaiting a collision test per phase
+constexpr int kMaxK = 128;  // in-radius candidates kept in LDS (more spill to the HBM list)
+constexpr int kRnd = 256;   // random doubles staged in LDS
+constexpr int kMaxH = 512;  // coarse in-radius hits staged in LDS (more are resolved inline)
 constexpr int kBins = 16;      // obstacle bins per axis over the map
 constexpr int kLdsBytes = 160 * 1024;  // the CU's LDS
 constexpr int kRrtMaxResident = 4;     // LDS tree shares per CU RRT honours from pmp_set_resident_per_cu
@@ -458,7 +441,7 @@ __device__ __forceinline__ double aget_c(const RrtShared& S, const AEntry* al, i
 typedef __attribute__((address_space(3))) uint32_t lds_xyq;
 
 template <bool STAR>
-__global__ __launch_bounds__(kNT, PMP_RRT_MINW) void rrt_kernel(RrtArgs A)
+__global__ __launch_bounds__(kNT, 1) void rrt_kernel(RrtArgs A)
 {
     __shared__ RrtShared S;
     const int lcap = A.lcap;
@@ -1039,7 +1022,7 @@ extern "C" int pmp_rrt_batch(pmp_ctx* ctx, void* stream, const pmp_rrt_params* p
     // RRT workgroup almost no tree in LDS: RRT honours at most kRrtMaxResident of it)
     int per = pmp_lds_share(ctx, 1);
     if (per > kRrtMaxResident) per = kRrtMaxResident;
-    if (per < PMP_RRT_PERCU) per = PMP_RRT_PERCU;  // narrower workgroups: two per CU
+    if (per < kPerCu) per = kPerCu;  // narrower workgroups: two per CU
     const long share = kLdsBytes / per;
     const int ob = obs_bytes(nr, nc, nb);
     int lcap = (int)(std::max(0L, share - (long)sizeof(RrtShared) - ob - 512) / 4) & ~63;

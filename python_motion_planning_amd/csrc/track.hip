@@ -209,13 +209,9 @@ __device__ __forceinline__ double max16(double t)
     return t;
 }
 
-// Where the ADMM keeps the inverse: registers (one row per lane, the default) or LDS (column-major,
-// 16 loads per x-update, 32 fewer live VGPRs: 26.2M vs 32.7M agent-steps/s at 8192 agents on the
-// same box).  A build-time switch for A/B runs (-DPMP_MPC_INV_LDS=0|1, make invlds).
-#ifndef PMP_MPC_INV_LDS
-#define PMP_MPC_INV_LDS 0
-#endif
-constexpr bool kInvLds = PMP_MPC_INV_LDS != 0;
+// The ADMM keeps the inverse in registers, one row per lane.  (In LDS, column-major -- 16 loads per
+// x-update, 32 fewer live VGPRs -- it ran 26.2M against 32.7M agent-steps/s at 8192 agents on the
+// same box.)
 
 // Minv = (H + sigma I + rho A'A)^-1, row v in this lane (rows/cols >= n are the identity).
 // A'A[2k+c][2k'+c'] = [c == c'] (m - max(k, k')) + [2k+c == 2k'+c'].
@@ -225,10 +221,8 @@ constexpr bool kInvLds = PMP_MPC_INV_LDS != 0;
 // operations, value for value, as eliminating on M and I side by side.  k is a run-time loop: the
 // elimination keeps only its own row live (an unrolled one lets the scheduler hoist every broadcast).
 __device__ __forceinline__ void build_inverse(const double* Hrow, int v, int n, int m, double sigma, double rho,
-                                              double* Icol, double* prow, double (&Ireg)[16])
+                                              double* prow, double (&A)[16])
 {
-    double Aloc[16];
-    double (&A)[16] = kInvLds ? Aloc : Ireg;  // the register build eliminates in place
     // opaque to the optimiser: nothing of the build is hoisted out of the ADMM loop around it (the
     // hoisted H row and per-column constants would stay live through every iteration)
     asm volatile("" : "+v"(v) : : "memory");
@@ -261,12 +255,6 @@ __device__ __forceinline__ void build_inverse(const double* Hrow, int v, int n, 
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
-    // the inverse, column-major for the agent (column c at Icol[16 c]): the x-update's loads of one
-    // column by the row's 16 lanes are one contiguous 128 B
-    if (kInvLds) {
-#pragma unroll
-        for (int c = 0; c < 16; c++) Icol[16 * c + v] = A[c];
-    }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 }
 
@@ -282,10 +270,7 @@ struct MpcIn {
 
 constexpr int kRows = 4;  // agents per wave
 // LDS doubles per wave of mpc_rows: an H per row, then a pivot row per row
-// (an H per row, then a pivot row per row, then an inverse per row at a 264-double stride: the
-// four rows' column loads fall in different LDS bank windows)
-constexpr int kInvStride = 264;
-constexpr int kMpcLds = kRows * 256 + kRows * 16 + (kInvLds ? kRows * kInvStride : 0);
+constexpr int kMpcLds = kRows * 256 + kRows * 16;
 
 // MPC.mpcControl (mpc.py:111-214) for the agents of the wave's four rows, called by the whole wave
 // (the MFMA needs all lanes); `need` (row-uniform) selects the rows whose agent solves now, the other
@@ -426,13 +411,12 @@ __device__ MpcResult mpc_rows(bool need, const MpcIn& I, double& up0, double& up
         // residual checks)
         const double* Hrow = Hs + 16 * v;
         double* prow = Hs_all + kRows * 256 + 16 * row;  // the agent's pivot row
-        double* Icol = Hs_all + kRows * 256 + kRows * 16 + kInvStride * row;  // the agent's inverse
 
         // ---- ADMM (the OSQP algorithm, unscaled), the row's agent: rows finish independently
         double rho = M.rho;
         const double sigma = M.sigma, alpha = M.alpha;
         double Ireg[16];
-        build_inverse(Hrow, v, n, m, sigma, rho, Icol, prow, Ireg);
+        build_inverse(Hrow, v, n, m, sigma, rho, prow, Ireg);
         double z1 = 0.0, z2 = 0.0, y1 = 0.0, y2 = 0.0;
         int status = 1, it = 0, cnt_c = 0, cnt_a = 0;
         while (it < M.max_iter) {
@@ -445,7 +429,7 @@ __device__ MpcResult mpc_rows(bool need, const MpcIn& I, double& up0, double& up
             double xt = 0.0;
             for16([&](auto cc) {
                 constexpr int c = decltype(cc)::value;
-                xt += (kInvLds ? Icol[16 * c + v] : Ireg[c]) * bc16<c>(rhs);
+                xt += Ireg[c] * bc16<c>(rhs);
             });
             xt = act ? xt : 0.0;
             const double zt1 = prefix16(xt);
@@ -485,7 +469,7 @@ __device__ MpcResult mpc_rows(bool need, const MpcIn& I, double& up0, double& up
                 const double rn = lp::clampd(rho * sqrt(pn / (dn + 1e-30)), 1e-6, 1e6);
                 if (rn > rho * M.adaptive_tol || rn < rho / M.adaptive_tol) {
                     rho = rn;
-                    build_inverse(Hrow, v, n, m, sigma, rho, Icol, prow, Ireg);
+                    build_inverse(Hrow, v, n, m, sigma, rho, prow, Ireg);
                 }
             }
         }

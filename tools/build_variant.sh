@@ -1,6 +1,6 @@
 #!/bin/bash
-# A/B builds: libpmp_hip_<name>.so with extra compile flags on the listed sources, the other objects
-# shared with the default build (make first).  Run here (CPU container), not on the GPU box:
+# Variant builds (the diagnostics): libpmp_hip_<name>.so with extra compile flags on the listed sources,
+# the other objects shared with the default build; the source list is csrc/Makefile's SRCS.  Run here (CPU container), not on the GPU box:
 #   bash tools/build_variant.sh <name> "<-D flags>" astar2d_mq.hip [more.hip ...]
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -11,7 +11,8 @@ VO=$R/build/var_$NAME
 mkdir -p $VO
 make -s -C $C -j8
 objs=()
-for f in pmp_ctx astar2d astar2d_mq astar2d_sq astar3d dwa track rrt dstar dstar3d lpa lpa3d totp3d; do
+for src in $(make -s -C $C print-srcs); do
+  f=${src%.hip}
   hit=0
   for s in "$@"; do [ "$s" = "$f.hip" ] && hit=1; done
   if [ $hit = 1 ]; then
