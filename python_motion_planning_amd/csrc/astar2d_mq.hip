@@ -424,11 +424,13 @@ __device__ __forceinline__ void pop_leaf(const GHeap& h, const Walk& wk, int n, 
 //       b..Kd-1 with X < heap[q_L] move down one level, X lands at level b.
 // One load round (lane L: heap[q_L] and its sibling; lane 15 of a pop: heap[n - 1], the new last),
 // a ballot for b, the stores, the bits of the changed levels' parents.  Returns b; lane L's new
-// heap[q_L] in (nf, nc, nk) (for the caller's cached parents).
-template <bool T2LDS, int HEUR>
+// heap[q_L] in (nf, nc, nk) (for the caller's cached parents).  mid() runs between the issue of the
+// load round and its first use: the caller's own loads of the step, which do not depend on the heap's.
+template <bool T2LDS, int HEUR, class Mid>
 __device__ __forceinline__ int path_op(const GHeap& h, lmask mon, lmask mpop, uint32_t Q, int Kd, int n, double Xf, uint32_t Xc,
                                        uint32_t Xk, int gl, int gb, double& lastf, uint32_t& lastc, uint32_t& lastk,
-                                       double& rootf, uint32_t& rootc, double& nf, uint32_t& nc, uint32_t& nk, uint32_t cwL)
+                                       double& rootf, uint32_t& rootc, double& nf, uint32_t& nc, uint32_t& nk, uint32_t cwL,
+                                       Mid&& mid)
 {
     // the lane predicates as lane masks (scalar logic, lm / lb): the step is VALU-issue-bound
     const bool lvl = gl <= Kd;
@@ -455,6 +457,7 @@ __device__ __forceinline__ int path_op(const GHeap& h, lmask mon, lmask mpop, ui
         offq = spill_off_cw(h, l15 ? cwK : cwL, l15 ? n - 1 : q);
         la.issue_off(h, lda ? q : (l15 ? n - 1 : 0), offq);
         ls.issue_off(h, hass ? si : 0, offq ^ sib_xor(cwL));
+        mid();
         la.get<HEUR>(Vf, Vc, Vk);
         ls.get<HEUR>(Sf, Sc, Sk);
     }
@@ -612,6 +615,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA ? 3 : 
     double pf8 = 0.0;
     uint32_t pk8 = 0u;
     int n0 = 0;
+    // The stale hint.  A pop whose cell is already CLOSED only rotates the heap, and what the next pop
+    // will take is known a step ahead: a pop's new root is the path's level-1 node, heap[1] or
+    // heap[2] by the root's choice bit, unless the old last lands at level 0.  So a pop loads that
+    // node's cell-state byte on lane 9 of its own 3x3 round (it returns with the round, nothing waits
+    // for it), and the step's end makes it Mstale: the byte says CLOSED (CLOSED only grows inside a
+    // query), or this step's own expansion closed that very cell.  A group in Mstale pops without
+    // the 3x3 round, G[pusher] and the parent prefetch, and a step whose pops are all stale issues
+    // none of the round's instructions but that byte's.  Every other group -- a root known to be
+    // open (a new query's start, a push that reached level 0) or not looked up (the old last at
+    // level 0) -- runs the pop's own centre test as before, so only a wrong "stale" could change a
+    // result, and a bit is set nowhere but from the root's own cell in the query's epoch.
+    lmask Mstale = 0ull;  // the group's root is CLOSED in this query
 
     for (;;) {
         // ---- groups without a query take the next one (or retire)
@@ -715,6 +730,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA ? 3 : 
                 const int k = __popc(run);
                 n += k;
                 npush += k;
+                // the heap's peak: a group whose run empties its pushes pops in this same step, before
+                // the step's end samples n
+                maxn = n > maxn ? n : maxn;
                 pend &= ~run;
                 wave_sync_mem();
             }
@@ -749,50 +767,73 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA ? 3 : 
             Q = (uint32_t)n + 1u;
             Kd = 31 - __clz((int)Q);
         }
+        const lmask Mskip = Mpop & Mstale;  // this step's pops known to be stale
+        uint32_t hidx = 0u;                 // cell-state index of the pop's new root (the path's level 1)
         if (pop) {
-            // ---- heappop (a_star.py:54), with the 3x3 round and the parent prefetch issued first
+            // ---- heappop (a_star.py:54): the leaf first, so that the heap's loads go out first
             npop++;
             n -= 1;
             n0 = n;
             const int ndir = cm_dir<HEUR>(ncm);
             x = ndir == 8 ? sx : gx - cm_dx<HEUR>(ncm);
             y = ndir == 8 ? sy : gy - cm_dy<HEUR>(ncm);
-            const bool has_pusher = THETA ? ndir != 8 : ndir < 8;
-            const int pm = ndir & 7;  // the pusher's motion
             nlin = (uint32_t)x * (uint32_t)H + (uint32_t)y;
-            // every lane issues all three loads (lanes that need none read index 0): no branch per
-            // lane class, so no load destination is zero-filled under another exec mask
-            {
-                const int cx = x + blk_dx, cy = y + blk_dy;
-                const bool in_occ = gl < 9 && (unsigned)cx < (unsigned)W && (unsigned)cy < (unsigned)H;
-                const uint32_t ci = in_occ ? (uint32_t)cx * (uint32_t)H + (uint32_t)cy : 0u;
-                const uint32_t cti = in_occ ? cst_idx(cx, cy, tH) : 0u;
-                const uint32_t pusher = !has_pusher ? 0u
-                                        : THETA     ? gix(x - mot_x(pm), y - mot_y(pm))
-                                                    : nlin - (uint32_t)(mot_x(pm) * H + mot_y(pm));
-                const uint32_t gi = (!GZERO && gl == 12) ? pusher : 0u;
-                const uint32_t ow = occ[ci >> 5];
-                blk_c = cst[cti];
-                gpar = GZERO ? 0.0 : G[gi];
-                if (THETA) ppar = Pc[gl == 13 ? pusher : 0u];
-                blk_sh = (int)(ci & 31u);
-                blk_w = ow;
-            }
             if (n > 0) pop_leaf<T2LDS>(hp, wk, n, gb, Q, Kd);
+            // the stale hint of the next pop: the path's level-1 node (heap[1] or heap[2], in LDS)
+            // becomes the root unless the old last lands at level 0; lane 9 of the 3x3 round loads its
+            // cell's state as of now (the step's end adds what this step's own expansion closes)
+            // (never the start's own code, dir 8: that entry is popped while it is alone)
+            {
+                const bool has1 = n > 1;  // Kd >= 1
+                const uint32_t c1 = hp.C[has1 ? (int)(Q >> (Kd - 1)) - 1 : 0];
+                hidx = has1 ? cst_idx(gx - cm_dx<HEUR>(c1), gy - cm_dy<HEUR>(c1), tH) : 0u;
+            }
         }
         // the pushes will take positions n0, n0 + 1, ...: their parents, while all 8 share a depth
-        Mpc = (Mpc & ~Mpop) | (Mpop & lm(n0 > 0) & lm(__clz(n0 + 1) == __clz(n0 + 8)));
+        // (none follow a stale pop)
+        Mpc = (Mpc & ~Mpop) | (Mpop & ~Mskip & lm(n0 > 0) & lm(__clz(n0 + 1) == __clz(n0 + 8)));
         const int pp = (n0 + (gl & 7) - 1) >> 1;  // lanes 0..7: parent of position n0 + lane
         {
             const int pi = lb(Mpop & Mpc & kLanesLt8) ? pp : 0;
             pld.issue_off(hp, pi, soff(pi));
         }
+        // the pop's loads beside the heap operation's own, issued behind those (path_op's mid): they
+        // are read after the operation
+        auto side_loads = [&]() {
+            if (pop) {
+                // the 3x3 round: every lane issues all three loads (lanes that need none, and lanes
+                // 0..8 of a stale pop, read index 0): no branch per lane class, so no load destination
+                // is zero-filled under another exec mask.  Lane 9 loads the hint's byte; when every pop
+                // of the wave is stale the round is that byte alone.
+                uint32_t cti = gl == 9 ? hidx : 0u;
+                if ((Mpop & ~Mskip) != 0ull) {
+                    const int ndir = cm_dir<HEUR>(ncm);
+                    const bool use = !lb(Mskip);
+                    const bool has_pusher = use && (THETA ? ndir != 8 : ndir < 8);
+                    const int pm = ndir & 7;  // the pusher's motion
+                    const int cx = x + blk_dx, cy = y + blk_dy;
+                    const bool in_occ = use && gl < 9 && (unsigned)cx < (unsigned)W && (unsigned)cy < (unsigned)H;
+                    const uint32_t ci = in_occ ? (uint32_t)cx * (uint32_t)H + (uint32_t)cy : 0u;
+                    cti = in_occ ? cst_idx(cx, cy, tH) : cti;
+                    const uint32_t pusher = !has_pusher ? 0u
+                                            : THETA     ? gix(x - mot_x(pm), y - mot_y(pm))
+                                                        : nlin - (uint32_t)(mot_x(pm) * H + mot_y(pm));
+                    const uint32_t gi = (!GZERO && gl == 12) ? pusher : 0u;
+                    const uint32_t ow = occ[ci >> 5];
+                    gpar = GZERO ? 0.0 : G[gi];
+                    if (THETA) ppar = Pc[gl == 13 ? pusher : 0u];
+                    blk_sh = (int)(ci & 31u);
+                    blk_w = ow;
+                }
+                blk_c = cst[cti];
+            }
+        };
         const lmask Mop = Mpush | (Mpop & lm(n > 0));
         double nf = 0.0;
         uint32_t nc = 0u, nk = 0u;
         int b = 0;
         b = path_op<T2LDS, HEUR>(hp, Mop, Mpop, Q, Kd, n, Xf, Xc, Xk, gl, gb, lastf, lastc, lastk, rootf, rootc, nf, nc,
-                                 nk, cwL);
+                                 nk, cwL, side_loads);
         {
             double f8;
             uint32_t c8, k8;
@@ -820,7 +861,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA ? 3 : 
         //      goal test, getNeighbor (a_star.py:57-82)
         // lanes 0..8: the cell is in the grid
         const lmask Mblk = kLanesLt9 & lm((unsigned)(x + blk_dx) < (unsigned)W) & lm((unsigned)(y + blk_dy) < (unsigned)H);
-        if (pop) {
+        uint32_t selfdup = 0u;  // the step expanded its node and the new root is a duplicate of that cell
+        if (lb(Mpop & ~Mskip)) {  // a stale pop loaded nothing and is CLOSED
             const uint32_t occ9 =
                 (uint32_t)((kLanesLt9 & (~Mblk | lm(((blk_w >> blk_sh) & 1u) != 0u))) >> gb) & 0x1FFu;
             // a cell is CLOSED in this query when its byte's high nibble is the epoch and its low nibble
@@ -829,6 +871,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA ? 3 : 
             const double gp = bcf<12>(gpar);
             if (!(cls9 & 16u)) {  // node.current not in CLOSED (a_star.py:57-58)
                 const int ndir = cm_dir<HEUR>(ncm);
+                selfdup = ((rootc ^ ncm) >> dbits<HEUR>()) == 0u;  // the codes' dx and dy agree
                 double gnode = (GZERO || ndir == 8) ? 0.0 : gp + ((ndir & 1) ? kSqrt2 : 1.0);
                 // THETA: the node's parent (cell, coordinates, g) and its expand-record code
                 uint32_t par_lin = nlin;
@@ -975,6 +1018,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA ? 3 : 
                 }
             }
             pend = 0u;
+        }
+
+        // ---- the stale hint of the next pop.  Every change of the root drops the old one: a pop, a
+        //      push that reached level 0 (an item of the current expansion: its cell was open then
+        //      and nothing has expanded since), the query's end (the next query's root is its start,
+        //      in a new epoch).  A push below level 0 and a trivial-push run keep the root and the
+        //      hint.  A pop whose path moved up (b >= 1) made its level-1 node the root: stale if hb,
+        //      that cell's state before this step, says CLOSED, or if this step expanded and the
+        //      cell is the one it closed (the codes' dx and dy fields agree; the start's own code, dir
+        //      8, names its cell otherwise, and no duplicate of it is looked at).  A pop with b == 0
+        //      (the old last at level 0) leaves the root not looked up.
+        {
+            const lmask Mb0 = lm(b == 0);
+            const uint32_t hb = bc<9>(blk_c);
+            const lmask Mcl1 = lm((hb >> 4) == ep) & lm((hb & 15u) != 0u);
+            Mstale = (Mstale & ~(Mpop | Mend | (Mpush & Mb0))) |
+                     (Mop & Mpop & ~Mend & ~Mb0 & (Mcl1 | lm(selfdup != 0u)));
         }
     }
     if (gl == 0) epoch_all[slot] = ep;

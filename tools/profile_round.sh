@@ -15,6 +15,9 @@ OUT=$R/gpurun_out
 mkdir -p $OUT/prof_kt $OUT/prof_fetch $OUT/prof_write $OUT/prof_mfma $OUT/prof_issue
 cd /tmp && export TMPDIR=/tmp
 SHORT="--full --no-cpu-baseline --warmup 1 --rrt-steps 1 --track-steps 1 --control-steps 2 --graph-steps 12 --dstar-steps 2 --dyn3d-steps 6"
+# LEGS=none: the counter passes run the headline alone (a change to its kernel only); the summary then
+# holds that workload alone
+[ -z "$LEGS" ] || SHORT="$SHORT --legs $LEGS"
 # PASSES=kt / pmc / issue / all (separate gpurun calls fit the per-call limit better than one)
 P=${PASSES:-all}
 [ "$P" = pmc ] || [ "$P" = issue ] || timeout -k 10 700 rocprofv3 --kernel-trace --stats -d $OUT/prof_kt -o run -- python3 $R/bench.py --full --steps 20 --warmup 5 \
@@ -31,7 +34,7 @@ timeout -k 10 500 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WA
     SQ_WAIT_INST_ANY SQ_WAVES GRBM_GUI_ACTIVE -d $OUT/prof_issue -o run -- python3 $R/bench.py $SHORT \
     --detail-out $OUT/prof_issue/detail.json > $OUT/bench_issue.json 2> $OUT/bench_issue.err
 # MFMA utilisation of the MPC tracking kernels (track_mpc_solve carries the assembly): its own pass
-timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES -d $OUT/prof_mfma -o run \
+[ "$LEGS" = none ] || timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES -d $OUT/prof_mfma -o run \
     -- python3 $R/bench.py --full --no-cpu-baseline --legs mpc --steps 1 --warmup 1 --track-steps 2 \
     --detail-out $OUT/prof_mfma/detail.json > $OUT/bench_mfma.json 2> $OUT/bench_mfma.err
 fi
