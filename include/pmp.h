@@ -149,6 +149,45 @@ int pmp_jps3d_batch(pmp_ctx* ctx, void* stream, const uint32_t* occ_bits, int pe
                     int32_t* path_len, uint32_t* path, int path_cap, int32_t* n_expanded, uint32_t* expand,
                     uint32_t* expand_parent, double* expand_g, int expand_cap, int64_t* counters, int32_t* status);
 
+/*
+ * Batched 2D Jump Point Search.  Replaces JPS.plan (global_planner/graph_search/jps.py:38-83):
+ * heappop under Node.__lt__ with CPython heapq's tie behaviour (the heap array equals CPython's after
+ * every push and pop), a pop skipped when its cell is in CLOSED (:56-57, no g comparison), the goal
+ * test (:60-63), the 8 jump() results (:85-121, forced neighbours :123-164) in the motion order of
+ * env.py:52-55, each kept when its cell is not in CLOSED (:69) and pushed in that order until the
+ * goal has been pushed (:74-80), then CLOSED[node.current] = node (:82).  g(jump point) adds the
+ * motion's cost (1 or math.sqrt(2)) once per step of the jump (Node.__add__ at :97), h is
+ * GraphSearcher.h; cost and path by AStar.extractPath over the CLOSED parents (a_star.py:98-117):
+ * math.hypot per leg, accumulated goal -> start; the path lists jump points only.  jump() is
+ * evaluated in its collapsed form (csrc/jps2d.hip): an axis ray returns the first goal or forced
+ * cell before an obstacle, a diagonal ray the first cell before an obstacle that is the goal, forced,
+ * or the origin of an axis ray (along either component) that returns something; no corner test.
+ * Not reproduced: the reference's RecursionError on rays that nest deeper than Python's recursion
+ * limit (an empty 1100-wide room; such queries complete here), and its walk off a grid without
+ * border walls -- cells outside the grid count as obstacles, so results equal the reference's on
+ * grids whose border cells are obstacles (what Grid builds).
+ * occ_bits, heuristic, start_xy, goal_xy, cost, path (cell ids, goal first), path_len, n_expanded
+ * (len(CLOSED)) as pmp_astar2d_batch; W, H <= 8192.
+ *   expand         nullable [nq][expand_cap] u32 CLOSED cells in insertion order
+ *   expand_parent  nullable [nq][expand_cap] u32 each node's parent cell (the start's is the start);
+ *                  needs expand
+ *   expand_g       nullable [nq][expand_cap] f64 each node's g; needs expand
+ *   push_cap       pushes (= heap entries, each with its g, cell and parent) kept per query;
+ *                  0 = min(8 W H + 8, 2^20) (a cell closes once and pushes at most 8)
+ *   counters       nullable [nq][4] i64 the reference's pushes, pops, expansions (pops not skipped),
+ *                  max heap size
+ * status: 0 found; 1 OPEN emptied or an endpoint outside the grid (cost 0, path_len 0: the reference
+ * returns []; with an endpoint outside, n_expanded and the counters are 0 too); 2 path_cap overflow; 3 push_cap overflow (that query alone stops, nothing of it is
+ * valid but n_expanded and the CLOSED records written so far).
+ * Scheduling as the A* engines (pmp_astar2d_set_schedule, pmp_astar2d_set_priority), workers per CU
+ * by pmp_set_workers_per_cu (default 8), LDS heap share by pmp_set_resident_per_cu.
+ */
+int pmp_jps2d_batch(pmp_ctx* ctx, void* stream, const uint32_t* occ_bits, int W, int H, int heuristic,
+                    const int32_t* start_xy, const int32_t* goal_xy, int nq, double* cost,
+                    int32_t* path_len, uint32_t* path, int path_cap, int32_t* n_expanded,
+                    uint32_t* expand, uint32_t* expand_parent, double* expand_g, int expand_cap,
+                    int push_cap, int64_t* counters, int32_t* status);
+
 /* LocalPlanner.params (local_planner/local_planner.py:39-55), same names and units. */
 typedef struct {
     double dt;             /* TIME_STEP */

@@ -593,6 +593,53 @@ def jps3d_batch(occ, starts, goals, heuristic: str = "euclidean", path_cap: int 
     return out
 
 
+def jps2d_batch(occ, starts, goals, heuristic: str = "euclidean", path_cap: int | None = None,
+                expand_cap: int = 0, push_cap: int = 0, counters: bool = False, occ_bits=None):
+    """Batched JPS.plan (jps.py:38-83) on pmp_jps2d_batch (csrc/jps2d.hip).
+
+    occ: a Grid or a numpy uint8 [W, H] occupancy shared by the queries (or occ=(W, H) with a prebuilt
+    `occ_bits` device tensor).  starts, goals: [nq, 2] int.
+    Returns dict of device tensors: cost f64 [nq] (0 without a path), path_len i32 [nq], path i32
+    [nq, path_cap] (cell ids x*H + y of the jump points, goal first), n_expanded i32 (len(CLOSED)),
+    status i32 (0 found, 1 no path, 2 path_cap overflow, 3 push_cap overflow), and with expand_cap != 0
+    expand / expand_parent / expand_g [nq, expand_cap]: the CLOSED cells in insertion order, each
+    node's parent cell and g; optional counters i64 [nq, 4] (pushes, pops, expansions, max heap size).
+    push_cap: pushes (and heap entries) kept per query, 0 = the kernel's default.
+    """
+    torch = _lib.device_check()
+    L = _lib.load_library()
+    ctx = _lib.context()
+    if occ_bits is not None:
+        W, H = (int(occ[0]), int(occ[1])) if isinstance(occ, tuple) else (int(occ.shape[0]), int(occ.shape[1]))
+    elif hasattr(occ, "occupancy_words"):  # a Grid
+        W, H = int(occ.x_range), int(occ.y_range)
+        occ_bits = torch.as_tensor(occ.occupancy_words().view(np.int32), device="cuda")
+    else:
+        W, H = int(occ.shape[0]), int(occ.shape[1])
+        occ_bits = occ_bits_device(occ, torch)
+    s = _dev(torch, starts, torch.int32).reshape(-1, 2)
+    g = _dev(torch, goals, torch.int32).reshape(-1, 2)
+    nq = int(s.shape[0])
+    if path_cap is None:
+        path_cap = min(W * H + 1, 1 << 12)
+    i32 = dict(dtype=torch.int32, device="cuda")
+    out = dict(cost=torch.empty(nq, dtype=torch.float64, device="cuda"), path_len=torch.empty(nq, **i32),
+               path=torch.empty((nq, path_cap), **i32), n_expanded=torch.empty(nq, **i32),
+               status=torch.empty(nq, **i32))
+    out["expand"] = torch.empty((nq, expand_cap), **i32) if expand_cap else None
+    out["expand_parent"] = torch.empty((nq, expand_cap), **i32) if expand_cap else None
+    out["expand_g"] = torch.empty((nq, expand_cap), dtype=torch.float64, device="cuda") if expand_cap else None
+    out["counters"] = torch.empty((nq, 4), dtype=torch.int64, device="cuda") if counters else None
+    rc = L.pmp_jps2d_batch(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), W, H, 1 if heuristic == "manhattan" else 0,
+                           s.data_ptr(), g.data_ptr(), nq, out["cost"].data_ptr(), out["path_len"].data_ptr(),
+                           out["path"].data_ptr(), int(path_cap), out["n_expanded"].data_ptr(), _lib.ptr(out["expand"]),
+                           _lib.ptr(out["expand_parent"]), _lib.ptr(out["expand_g"]), int(expand_cap), int(push_cap),
+                           _lib.ptr(out["counters"]), out["status"].data_ptr())
+    _lib.check(ctx, rc, "pmp_jps2d_batch")
+    out["W"], out["H"] = W, H
+    return out
+
+
 def dstar3d_batch(occ, starts, goals, blocks=None, path_cap: int | None = None, expand_cap: int = 0,
                   max_process: int = 0, occ_bits=None):
     """Batched DStar3D (d_star3d.py:60-281): plan() and then one apply_dynamic_obstacles() per round

@@ -229,6 +229,62 @@ class LazyThetaStar(ThetaStar):
         return "Lazy Theta*"
 
 
+class JPS(AStar):
+    """Jump Point Search (jps.py:12-164) -- the search runs in the gfx950 kernel jps2d.hip.
+
+    Cells outside the grid count as obstacles (the reference walks off a grid without border walls;
+    Grid builds the walls), and a ray of any length completes (the reference raises RecursionError
+    once a ray nests deeper than Python's recursion limit).  SearchFactory()("jps", ...) keeps raising
+    NotImplementedError: tests/test_no_fallback.py pins the factory's names, construct the class."""
+
+    def __init__(self, start: tuple, goal: tuple, env: Grid, heuristic_type: str = "euclidean") -> None:
+        super().__init__(start, goal, env, heuristic_type)
+
+    def __str__(self) -> str:
+        return "Jump Point Search(JPS)"
+
+    def plan(self) -> tuple:
+        """(cost, path goal -> start as (x, y) jump points, expand) or ([], [], []) (jps.py:38-83).
+        expand is list(CLOSED.values()): Node(current, parent, g, h) in insertion order, h computed
+        here (the start's is the 0 it was built with)."""
+        W, H = self.env.x_range, self.env.y_range
+        s = tuple(int(v) for v in self.start.current)
+        g = tuple(int(v) for v in self.goal.current)
+        path_cap = expand_cap = 1 << 12
+        while True:
+            r = batch.jps2d_batch(self.env, np.array([s], np.int32), np.array([g], np.int32), self.heuristic_type,
+                                  path_cap=path_cap, expand_cap=expand_cap)
+            st, ne, plen = int(r["status"][0]), int(r["n_expanded"][0]), int(r["path_len"][0])
+            if st == 3:  # the default push capacity overflowed: every cell pushes at most 8 times
+                r = batch.jps2d_batch(self.env, np.array([s], np.int32), np.array([g], np.int32), self.heuristic_type,
+                                      path_cap=W * H + 1, expand_cap=W * H, push_cap=8 * W * H + 8)
+                st, ne, plen = int(r["status"][0]), int(r["n_expanded"][0]), int(r["path_len"][0])
+                break
+            if st == 2 or ne > expand_cap:  # exact sizes
+                path_cap, expand_cap = max(path_cap, plen), max(expand_cap, ne)
+                continue
+            break
+        if st == 1:
+            return [], [], []
+        if st != 0:
+            raise RuntimeError(f"{self} kernel status {st}")
+        dec = lambda c: (int(c) // H, int(c) % H)  # noqa: E731
+        path = [dec(c) for c in r["path"][0, :plen].cpu().numpy()]
+        expand = []
+        for c, p, gv in zip(r["expand"][0, :ne].cpu().numpy(), r["expand_parent"][0, :ne].cpu().numpy(),
+                            r["expand_g"][0, :ne].cpu().numpy()):
+            node = Node(dec(c), dec(p), float(gv), 0)
+            if len(expand):
+                node.h = self.h(node, self.goal)
+            expand.append(node)
+        return float(r["cost"][0]), path, expand
+
+    @classmethod
+    def plan_batch(cls, occ, starts, goals, heuristic_type: str = "euclidean", **kw):
+        """Batched plan over one occupancy grid; returns the device-tensor dict of batch.jps2d_batch."""
+        return batch.jps2d_batch(occ, starts, goals, heuristic_type, **kw)
+
+
 class LPAStar(GraphSearcher):
     """Lifelong Planning A* (lpa_star.py:39-230): plan() is the initial computeShortestPath +
     extractPath on the gfx950 kernel lpa.hip (U with the reference's list semantics).  Interactive
