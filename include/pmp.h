@@ -487,6 +487,41 @@ int pmp_rrt_batch(pmp_ctx* ctx, void* stream, const pmp_rrt_params* p, const dou
                   int32_t* path_len, double* path_xy, int path_cap, int64_t* draws, int32_t* status,
                   int64_t* counters);
 
+/*
+ * Batched Informed RRT*.  Replaces InformedRRT.plan and generateRandomNode
+ * (global_planner/sample_search/informed_rrt.py:74-152) on the RRT* iteration of pmp_rrt_batch: the loop
+ * runs all sample_num iterations, the goal stays in the tree as an ordinary node once connected (every
+ * later connection overwrites its parent and g), the best connection's cost and path are kept, and once
+ * a path exists samples come from Ellipse.transform(c_best / 2) applied to points of the unit disk.
+ * One workgroup per query.  All arrays are device pointers; those not listed are pmp_rrt_batch's.
+ *   p                     pmp_rrt_params; star is ignored (always RRT*)
+ *   ellipse [nq][5]       per query: the ellipse's centre x, y, cos(theta), sin(theta) of
+ *                         theta = -np.arctan2(gy - sy, gx - sx), and c = hypot(start, goal) / 2 -- computed
+ *                         by the caller with the reference's own numpy expressions (np.arctan2 is not
+ *                         libm's atan2 to the last bit, so the kernel takes theta's cos / sin as given)
+ *   rnd [nq][rnd_stride]  the np.random double stream: 1 or 3 doubles per iteration until the first
+ *                         connection, then 2 per try of the rejection sampler -- unbounded, so a query
+ *                         that reaches the end of its stream reports status 3 (re-run with a longer one)
+ *   tree_*, n_nodes       out: sample_list in insertion order; the goal sits at goal_slot with its final
+ *                         parent and g (not necessarily the best path's)
+ *   best_cost [nq]        out: the lowest goal.g at any connection, +inf when never connected
+ *   n_finds [nq]          out: completed connections (extractPath calls that returned)
+ *   goal_slot [nq]        out: the goal's index in the tree, -1 when never connected
+ *   path_len [nq], path_xy [nq][path_cap][2]   out: extractPath goal -> start of the best connection
+ *   draws [nq] i64        out: doubles consumed, rejected tries included
+ *   status [nq]           0 connected at least once, 1 never (returns (inf, None, nodes)), 2 path_cap
+ *                         overflow, 3 tree_cap / stream / candidate-list overflow, 4 a connection closed a
+ *                         parent cycle (the reference's extractPath never returns; the tree is left as
+ *                         at that moment, best_cost / path hold the best connection before it)
+ */
+int pmp_informed_rrt_batch(pmp_ctx* ctx, void* stream, const pmp_rrt_params* p, const double* rect, int nr,
+                           const double* circ, int nc, const double* bnd, int nb, const double* start_xy,
+                           const double* goal_xy, const double* ellipse, int nq, const double* rnd,
+                           int64_t rnd_stride, int tree_cap, double* tree_xy, double* tree_g,
+                           int32_t* tree_parent, int32_t* n_nodes, double* best_cost, int32_t* n_finds,
+                           int32_t* goal_slot, int32_t* path_len, double* path_xy, int path_cap, int64_t* draws,
+                           int32_t* status, int64_t* counters);
+
 /* TrajectoryConstraints (trajectory/trajectory_base.py:30-45) and TimeOptimalTrajectory3D's
  * path_resolution (trajectory/time_optimal_trajectory.py:17-29) */
 typedef struct {

@@ -68,6 +68,8 @@ SIGNATURES = {
                                           _vp]),
     "pmp_rrt_batch": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, ctypes.c_int64, _i, _vp, _vp,
                            _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "pmp_informed_rrt_batch": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, ctypes.c_int64,
+                                    _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "pmp_track_step_batch": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
                                   _vp]),
     "pmp_totp3d_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,

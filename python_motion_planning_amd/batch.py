@@ -6,6 +6,7 @@ each one launches the gfx950 kernels of libpmp_hip.so asynchronously on the curr
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 
@@ -511,6 +512,63 @@ def rrt_batch(env, starts, goals, rnd, sample_num: int, star: bool = True, max_d
                          out["path"].data_ptr(), path_cap, out["draws"].data_ptr(), out["status"].data_ptr(),
                          _lib.ptr(out["counters"]))
     _lib.check(ctx, rc, "pmp_rrt_batch")
+    return out
+
+
+def ellipse_constants(starts, goals) -> np.ndarray:
+    """[nq, 5] per query: the centre, cos / sin of theta and c of Ellipse.transform
+    (informed_rrt.py:20-33, 67-69), each with the reference's own scalar numpy expression (np.arctan2
+    differs from libm's atan2 in the last bit of some inputs, so theta is not recomputed on the device)."""
+    s = np.asarray(starts, np.float64).reshape(-1, 2)
+    g = np.asarray(goals, np.float64).reshape(-1, 2)
+    out = np.empty((len(s), 5), np.float64)
+    for q, (p1, p2) in enumerate(zip(s.tolist(), g.tolist())):
+        theta = -np.arctan2(p2[1] - p1[1], p2[0] - p1[0])
+        out[q] = ((p1[0] + p2[0]) / 2, (p1[1] + p2[1]) / 2, np.cos(theta), np.sin(theta),
+                  math.hypot(p2[0] - p1[0], p2[1] - p1[1]) / 2)
+    return out
+
+
+def informed_rrt_batch(env, starts, goals, rnd, sample_num: int, max_dist: float = 0.5, radius: float = 12.0,
+                       delta: float = 0.5, goal_sample_rate: float = 0.05, path_cap: int | None = None,
+                       counters: bool = False):
+    """Batched Informed RRT* plans (informed_rrt.py:74-152) on one Map.
+    rnd: [nq, stride] f64 random streams (RandomState.random_sample order).  The ellipse sampler's draw
+    count is unbounded: a query that reaches the end of its stream reports status 3 (re-run it with a
+    longer stream; 4*sample_num+64 is enough for most).
+    Returns dict of device tensors: tree_xy [nq,cap,2], tree_g, tree_parent, n_nodes, best_cost (inf:
+    never connected), n_finds, goal_slot (-1: never connected), path_len, path [nq,path_cap,2] (the best
+    connection's, goal -> start), draws, status."""
+    torch = _lib.device_check()
+    L = _lib.load_library()
+    ctx = _lib.context()
+    rect, circ, bnd = map_arrays(env, torch)
+    s = _dev(torch, starts, torch.float64).reshape(-1, 2)
+    g = _dev(torch, goals, torch.float64).reshape(-1, 2)
+    ell = torch.as_tensor(ellipse_constants(s.cpu().numpy(), g.cpu().numpy()), device="cuda")
+    nq = int(s.shape[0])
+    rnd = _dev(torch, rnd, torch.float64).reshape(nq, -1)
+    cap = int(sample_num) + 2
+    path_cap = cap if path_cap is None else int(path_cap)
+    f64 = dict(dtype=torch.float64, device="cuda")
+    i32 = dict(dtype=torch.int32, device="cuda")
+    out = dict(tree_xy=torch.empty((nq, cap, 2), **f64), tree_g=torch.empty((nq, cap), **f64),
+               tree_parent=torch.empty((nq, cap), **i32), n_nodes=torch.empty(nq, **i32),
+               best_cost=torch.empty(nq, **f64), n_finds=torch.empty(nq, **i32), goal_slot=torch.empty(nq, **i32),
+               path_len=torch.empty(nq, **i32), path=torch.empty((nq, max(path_cap, 1), 2), **f64),
+               draws=torch.empty(nq, dtype=torch.int64, device="cuda"), status=torch.empty(nq, **i32),
+               counters=torch.zeros((nq, 4), dtype=torch.int64, device="cuda") if counters else None)
+    P = _lib.RRTParams(float(env.x_range), float(env.y_range), float(delta), float(max_dist), float(radius),
+                       float(goal_sample_rate), int(sample_num), 1)
+    rc = L.pmp_informed_rrt_batch(ctx, _lib.stream_ptr(), ctypes.byref(P), rect.data_ptr(), int(rect.shape[0]),
+                                  circ.data_ptr(), int(circ.shape[0]), bnd.data_ptr(), int(bnd.shape[0]),
+                                  s.data_ptr(), g.data_ptr(), ell.data_ptr(), nq, rnd.data_ptr(), int(rnd.shape[1]),
+                                  cap, out["tree_xy"].data_ptr(), out["tree_g"].data_ptr(),
+                                  out["tree_parent"].data_ptr(), out["n_nodes"].data_ptr(),
+                                  out["best_cost"].data_ptr(), out["n_finds"].data_ptr(), out["goal_slot"].data_ptr(),
+                                  out["path_len"].data_ptr(), out["path"].data_ptr(), path_cap,
+                                  out["draws"].data_ptr(), out["status"].data_ptr(), _lib.ptr(out["counters"]))
+    _lib.check(ctx, rc, "pmp_informed_rrt_batch")
     return out
 
 

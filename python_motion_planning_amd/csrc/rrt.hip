@@ -19,6 +19,13 @@
 //     c_i < G0 need a collision test to build that set; then every in-radius node decides its
 //     rewire (g_i > G_{i-1} + d_i and collision-free) independently;
 //  5. insert (a node landing exactly on an existing one replaces it, like the dict), goal test.
+//
+// Informed RRT* (informed_rrt.py:74-152) is the RRT* iteration with three changes, compiled in by
+// rrt_body's INF switch: once a path exists the sample comes from the ellipse of paths no longer than
+// the best one (rejection sampling in the unit disk, an affine map, a bounds test: a variable number
+// of draws); the loop does not stop at the goal, which stays in the tree as an ordinary node (nearest
+// scans find it, rewiring re-parents it, every later connection overwrites its parent and g); and the
+// cost and path of the best connection so far are kept.
 #include "localplan.h"
 
 namespace {
@@ -83,6 +90,12 @@ struct RrtArgs {
     TEntry* tlist;    // scratch [nq][cap]
     AEntry* alist;    // scratch [nq][cap]
     int lcap;         // nodes of the coarse copy held in LDS
+};
+
+struct InfArgs {  // Informed RRT* only
+    const double* ell;  // [nq][5]: ellipse centre x, y, cos(theta), sin(theta), c = c_min / 2
+    int32_t* n_finds;
+    int32_t* goal_slot;
 };
 
 struct RrtShared {
@@ -440,9 +453,11 @@ __device__ __forceinline__ double aget_c(const RrtShared& S, const AEntry* al, i
 
 typedef __attribute__((address_space(3))) uint32_t lds_xyq;
 
-template <bool STAR>
-__global__ __launch_bounds__(kNT, 1) void rrt_kernel(RrtArgs A)
+// one query's plan; INF: Informed RRT* (A.cost / A.path / A.path_len take the best connection's)
+template <bool STAR, bool INF>
+__device__ __forceinline__ void rrt_body(const RrtArgs& A, const InfArgs& I)
 {
+    static_assert(STAR || !INF, "Informed RRT* is an RRT* mode");
     __shared__ RrtShared S;
     const int lcap = A.lcap;
     const int q = blockIdx.x;
@@ -566,19 +581,55 @@ __global__ __launch_bounds__(kNT, 1) void rrt_kernel(RrtArgs A)
 #endif
 
     int64_t rb0 = 0, rb1 = 0;  // staged window [rb0, rb1) of the random stream
+    // the window restarts at the next draw (every thread holds the same cur: wave-uniform)
+    auto restage = [&]() {
+        __syncthreads();
+        rb0 = cur;
+        rb1 = rb0 + kRnd < A.stride ? rb0 + kRnd : A.stride;
+        for (int i = tid; i < (int)(rb1 - rb0); i += kNT) S.rbuf[i] = rnd[rb0 + i];
+        __syncthreads();
+    };
+    // Informed RRT* state, the same in every thread: the best connection's cost (c_best of
+    // informed_rrt.py:110, inf until the first one) and path length, the goal's slot in the tree (-1
+    // until it is connected), the connections made
+    double c_best = INFINITY;
+    int c_best_len = 0, gslot = -1, nfinds = 0;
+    bool path_over = false;
+    double ecx = 0.0, ecy = 0.0, ecos = 1.0, esin = 0.0, ec = 0.0;
+    if constexpr (INF) {
+        const double* e = I.ell + 5 * (size_t)q;
+        ecx = e[0]; ecy = e[1]; ecos = e[2]; esin = e[3]; ec = e[4];
+    }
     for (int it = 0; it < P.sample_num; it++) {
-        if (cur + 3 > A.stride) { status = PMP_CAP_OVERFLOW; break; }
-        if (cur + 3 > rb1) {
-            __syncthreads();
-            rb0 = cur;
-            rb1 = rb0 + kRnd < A.stride ? rb0 + kRnd : A.stride;
-            for (int i = tid; i < (int)(rb1 - rb0); i += kNT) S.rbuf[i] = rnd[rb0 + i];
-            __syncthreads();
-        }
         double sx = gx, sy = gy;
-        if (S.rbuf[cur++ - rb0] > P.goal_sample_rate) {
-            sx = lox + rgx * S.rbuf[cur++ - rb0];
-            sy = loy + rgy * S.rbuf[cur++ - rb0];
+        if (INF && c_best < INFINITY) {
+            // generateRandomNode's ellipse branch (informed_rrt.py:136-149): no goal-rate draw; tries
+            // of two draws each until a point of the unit disk maps into the map's sampling box.
+            // Ellipse.transform (informed_rrt.py:20-33) with a = c_best / 2: the host passes the
+            // centre, cos / sin of theta = -np.arctan2(..) and c as numpy computes them; T @ p rounds
+            // as OpenBLAS does, fma(t0, x, t1 * y) + t2 with the rounded products t0, t1.
+            // Every try takes two draws and the stream is finite: at most stride / 2 rounds.
+            const double ea = c_best / 2;
+            const double eb = sqrt(ea * ea - ec * ec);
+            const double t00 = ea * ecos, t01 = eb * esin, t10 = -ea * esin, t11 = eb * ecos;
+            bool got = false;
+            while (cur + 2 <= A.stride) {
+                if (cur + 2 > rb1) restage();
+                const double ux = -1.0 + 2.0 * S.rbuf[cur - rb0], uy = -1.0 + 2.0 * S.rbuf[cur + 1 - rb0];
+                cur += 2;
+                if (!(ux * ux + uy * uy < 1)) continue;
+                sx = fma(t00, ux, t01 * uy) + ecx;
+                sy = fma(t10, ux, t11 * uy) + ecy;
+                if (delta <= sx && sx <= P.x_range - delta && delta <= sy && sy <= P.y_range - delta) { got = true; break; }
+            }
+            if (!got) { status = PMP_CAP_OVERFLOW; break; }
+        } else {
+            if (cur + 3 > A.stride) { status = PMP_CAP_OVERFLOW; break; }
+            if (cur + 3 > rb1) restage();
+            if (S.rbuf[cur++ - rb0] > P.goal_sample_rate) {
+                sx = lox + rgx * S.rbuf[cur++ - rb0];
+                sy = loy + rgy * S.rbuf[cur++ - rb0];
+            }
         }
         c_iter++;
         c_scan += n;
@@ -943,6 +994,55 @@ __global__ __launch_bounds__(kNT, 1) void rrt_kernel(RrtArgs A)
         const double dg = lp::py_hypot(gx - nx, gy - ny);
         c_tests += dg <= P.max_dist;
         if (dg <= P.max_dist && !collision_block(S, nr, nc, nb, delta, nx, ny, gx, gy)) {
+            if constexpr (INF) {
+                // informed_rrt.py:103-110.  The first connection appends the goal (a node_new that
+                // landed exactly on the goal is replaced by it, like the dict entry); every connection
+                // sets goal.parent and goal.g, whether or not the path improves.
+                if (gslot < 0) {
+                    if (nx == gx && ny == gy) {
+                        gslot = slot;
+                    } else {
+                        if (n >= cap) { status = PMP_CAP_OVERFLOW; break; }
+                        gslot = n++;
+                        if (tid == 0) {
+                            tx[2 * gslot] = gx; tx[2 * gslot + 1] = gy;
+                            xq_store(gslot, qenc(gx, gy));
+                        }
+                    }
+                }
+                // thread 0: extractPath (rrt.py:133-151) from the goal, at most n + 1 nodes (a parent
+                // cycle never ends in the reference), copied out only when the cost improves.  The
+                // result travels through fields that are idle between the insert and the next scan.
+                if (tid == 0) {
+                    const double cg = G + lp::py_hypot(nx - gx, ny - gy);
+                    tg[gslot] = cg;
+                    tpar[gslot] = slot;
+                    const bool better = cg < c_best;
+                    double* out = A.path + (size_t)q * A.path_cap * 2;
+                    int v = gslot, plen = 0;
+                    bool reached = false;
+                    for (int s = 0; s <= n; s++) {
+                        if (better && plen < A.path_cap) { out[2 * plen] = tx[2 * v]; out[2 * plen + 1] = tx[2 * v + 1]; }
+                        plen++;
+                        if (v == 0) { reached = true; break; }
+                        v = tpar[v];
+                    }
+                    S.fflag = !reached ? 2 : better ? 1 : 0;
+                    S.newG = cg;
+                    S.nT2 = plen;
+                }
+                __syncthreads();
+                const int fr = S.fflag;
+                if (fr == 2) { status = PMP_REF_RAISES; break; }
+                nfinds++;
+                if (fr == 1) {
+                    c_best = S.newG;
+                    c_best_len = S.nT2;
+                    path_over = c_best_len > A.path_cap;
+                }
+                RSTAMP(7);
+                continue;
+            }
             if (n >= cap) { status = PMP_CAP_OVERFLOW; break; }
             if (tid == 0) {
                 tx[2 * n] = gx; tx[2 * n + 1] = gy; tg[n] = G + lp::py_hypot(nx - gx, ny - gy); tpar[n] = slot;
@@ -971,7 +1071,13 @@ __global__ __launch_bounds__(kNT, 1) void rrt_kernel(RrtArgs A)
         }
         int plen = 0;
         double c = 0.0;
-        if (status == PMP_FOUND) {
+        if constexpr (INF) {
+            if (status == PMP_NO_PATH && nfinds > 0) status = path_over ? PMP_PATH_OVERFLOW : PMP_FOUND;
+            plen = c_best_len;
+            c = c_best;
+            I.n_finds[q] = nfinds;
+            I.goal_slot[q] = gslot;
+        } else if (status == PMP_FOUND) {
             c = tg[n - 1];
             // extractPath (rrt.py:133-151): goal -> start through parents
             int v = n - 1;
@@ -990,6 +1096,42 @@ __global__ __launch_bounds__(kNT, 1) void rrt_kernel(RrtArgs A)
         A.cost[q] = c;
         A.status[q] = status;
     }
+}
+
+template <bool STAR>
+__global__ __launch_bounds__(kNT, 1) void rrt_kernel(RrtArgs A)
+{
+    rrt_body<STAR, false>(A, InfArgs{});
+}
+
+__global__ __launch_bounds__(kNT, 1) void informed_rrt_kernel(RrtArgs A, InfArgs I)
+{
+    rrt_body<true, true>(A, I);
+}
+
+// the per-call scratch and the LDS split of a launch: fills A's scratch pointers and lcap and the
+// dynamic LDS size (false with ctx's error set: out of memory)
+bool rrt_launch_setup(pmp_ctx* ctx, int nr, int nc, int nb, int nq, int tree_cap, RrtArgs& A, size_t& dyn)
+{
+    uint32_t* xyq = (uint32_t*)pmp_scratch(ctx, SCR_AUX0, sizeof(uint32_t) * (size_t)nq * tree_cap);
+    KEntry* kl = (KEntry*)pmp_scratch(ctx, SCR_AUX1, sizeof(KEntry) * (size_t)nq * tree_cap);
+    TEntry* tl = (TEntry*)pmp_scratch(ctx, SCR_AUX2, sizeof(TEntry) * (size_t)nq * tree_cap);
+    AEntry* al = (AEntry*)pmp_scratch(ctx, SCR_AUX3, sizeof(AEntry) * (size_t)nq * tree_cap);
+    if (!xyq || !kl || !tl || !al) return false;
+    // the coarse copy's LDS part: the workgroup's share of the CU's LDS (one workgroup per CU unless
+    // pmp_set_resident_per_cu leaves room for more: several in flight) beside its static state
+    // (ctx->resident_per_cu is shared with the one-wave planners, whose 16-32 per CU would leave an
+    // RRT workgroup almost no tree in LDS: RRT honours at most kRrtMaxResident of it)
+    int per = pmp_lds_share(ctx, 1);
+    if (per > kRrtMaxResident) per = kRrtMaxResident;
+    if (per < kPerCu) per = kPerCu;  // narrower workgroups: two per CU
+    const long share = kLdsBytes / per;
+    const int ob = obs_bytes(nr, nc, nb);
+    int lcap = (int)(std::max(0L, share - (long)sizeof(RrtShared) - ob - 512) / 4) & ~63;
+    if (lcap > tree_cap) lcap = (tree_cap + 63) & ~63;
+    A.xyq = xyq; A.klist = kl; A.tlist = tl; A.alist = al; A.lcap = lcap;
+    dyn = (size_t)ob + (size_t)lcap * 4;
+    return true;
 }
 
 }  // namespace
@@ -1011,23 +1153,9 @@ extern "C" int pmp_rrt_batch(pmp_ctx* ctx, void* stream, const pmp_rrt_params* p
         !tree_parent || !n_nodes || !cost || !path_len || (path_cap && !path_xy) || !draws || !status)
         return pmp_set_err(ctx, PMP_EINVAL, "pmp_rrt_batch: null pointer argument");
     PMP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    uint32_t* xyq = (uint32_t*)pmp_scratch(ctx, SCR_AUX0, sizeof(uint32_t) * (size_t)nq * tree_cap);
-    KEntry* kl = (KEntry*)pmp_scratch(ctx, SCR_AUX1, sizeof(KEntry) * (size_t)nq * tree_cap);
-    TEntry* tl = (TEntry*)pmp_scratch(ctx, SCR_AUX2, sizeof(TEntry) * (size_t)nq * tree_cap);
-    AEntry* al = (AEntry*)pmp_scratch(ctx, SCR_AUX3, sizeof(AEntry) * (size_t)nq * tree_cap);
-    if (!xyq || !kl || !tl || !al) return PMP_ENOMEM;
-    // the coarse copy's LDS part: the workgroup's share of the CU's LDS (one workgroup per CU unless
-    // pmp_set_resident_per_cu leaves room for more: several in flight) beside its static state
-    // (ctx->resident_per_cu is shared with the one-wave planners, whose 16-32 per CU would leave an
-    // RRT workgroup almost no tree in LDS: RRT honours at most kRrtMaxResident of it)
-    int per = pmp_lds_share(ctx, 1);
-    if (per > kRrtMaxResident) per = kRrtMaxResident;
-    if (per < kPerCu) per = kPerCu;  // narrower workgroups: two per CU
-    const long share = kLdsBytes / per;
-    const int ob = obs_bytes(nr, nc, nb);
-    int lcap = (int)(std::max(0L, share - (long)sizeof(RrtShared) - ob - 512) / 4) & ~63;
-    if (lcap > tree_cap) lcap = (tree_cap + 63) & ~63;
     RrtArgs A;
+    size_t dyn;
+    if (!rrt_launch_setup(ctx, nr, nc, nb, nq, tree_cap, A, dyn)) return PMP_ENOMEM;
     A.P = *p;
     A.rect = rect; A.circ = circ; A.bnd = bnd;
     A.nr = nr; A.nc = nc; A.nb = nb;
@@ -1035,13 +1163,48 @@ extern "C" int pmp_rrt_batch(pmp_ctx* ctx, void* stream, const pmp_rrt_params* p
     A.rnd = rnd; A.stride = rnd_stride; A.cap = tree_cap;
     A.txy = tree_xy; A.tg = tree_g; A.tpar = tree_parent; A.n_nodes = n_nodes;
     A.cost = cost; A.path_len = path_len; A.path = path_xy; A.path_cap = path_cap;
-    A.draws = draws; A.status = status; A.counters = counters; A.xyq = xyq; A.klist = kl;
-    A.tlist = tl; A.alist = al; A.lcap = lcap;
-    const size_t dyn = (size_t)ob + (size_t)lcap * 4;
+    A.draws = draws; A.status = status; A.counters = counters;
     if (p->star)
         hipLaunchKernelGGL(rrt_kernel<true>, dim3(nq), dim3(kNT), dyn, (hipStream_t)stream, A);
     else
         hipLaunchKernelGGL(rrt_kernel<false>, dim3(nq), dim3(kNT), dyn, (hipStream_t)stream, A);
+    PMP_HIP_CHECK(ctx, hipGetLastError());
+    return PMP_OK;
+}
+
+extern "C" int pmp_informed_rrt_batch(pmp_ctx* ctx, void* stream, const pmp_rrt_params* p, const double* rect, int nr,
+                                      const double* circ, int nc, const double* bnd, int nb, const double* start_xy,
+                                      const double* goal_xy, const double* ellipse, int nq, const double* rnd,
+                                      int64_t rnd_stride, int tree_cap, double* tree_xy, double* tree_g,
+                                      int32_t* tree_parent, int32_t* n_nodes, double* best_cost, int32_t* n_finds,
+                                      int32_t* goal_slot, int32_t* path_len, double* path_xy, int path_cap,
+                                      int64_t* draws, int32_t* status, int64_t* counters)
+{
+    if (!ctx) return PMP_EINVAL;
+    if (!p || nq < 0 || nr < 0 || nc < 0 || nb < 0 || nr > kMaxObs || nc > kMaxObs || nb > kMaxBnd)
+        return pmp_set_err(ctx, PMP_EINVAL, "pmp_informed_rrt_batch: bad params or obstacle counts (<= 256 rects, 256 circles, 8 boundary)");
+    if (p->sample_num < 0 || tree_cap < 2 || rnd_stride < 1 || path_cap < 0 || !(p->delta >= 0) || !(p->max_dist >= 0))
+        return pmp_set_err(ctx, PMP_EINVAL, "pmp_informed_rrt_batch: bad sample_num / tree_cap / rnd_stride / path_cap");
+    if (nq == 0) return PMP_OK;
+    if ((nr && !rect) || (nc && !circ) || (nb && !bnd) || !start_xy || !goal_xy || !ellipse || !rnd || !tree_xy ||
+        !tree_g || !tree_parent || !n_nodes || !best_cost || !n_finds || !goal_slot || !path_len ||
+        (path_cap && !path_xy) || !draws || !status)
+        return pmp_set_err(ctx, PMP_EINVAL, "pmp_informed_rrt_batch: null pointer argument");
+    PMP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    RrtArgs A;
+    size_t dyn;
+    if (!rrt_launch_setup(ctx, nr, nc, nb, nq, tree_cap, A, dyn)) return PMP_ENOMEM;
+    A.P = *p;
+    A.rect = rect; A.circ = circ; A.bnd = bnd;
+    A.nr = nr; A.nc = nc; A.nb = nb;
+    A.start = start_xy; A.goal = goal_xy; A.nq = nq;
+    A.rnd = rnd; A.stride = rnd_stride; A.cap = tree_cap;
+    A.txy = tree_xy; A.tg = tree_g; A.tpar = tree_parent; A.n_nodes = n_nodes;
+    A.cost = best_cost; A.path_len = path_len; A.path = path_xy; A.path_cap = path_cap;
+    A.draws = draws; A.status = status; A.counters = counters;
+    InfArgs I;
+    I.ell = ellipse; I.n_finds = n_finds; I.goal_slot = goal_slot;
+    hipLaunchKernelGGL(informed_rrt_kernel, dim3(nq), dim3(kNT), dyn, (hipStream_t)stream, A, I);
     PMP_HIP_CHECK(ctx, hipGetLastError());
     return PMP_OK;
 }

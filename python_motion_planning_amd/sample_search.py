@@ -1,5 +1,5 @@
-"""Sample-search planners: drop-in RRT / RRTStar (global_planner/sample_search/) on the gfx950
-kernel rrt.hip.
+"""Sample-search planners: drop-in RRT / RRTStar / InformedRRT (global_planner/sample_search/) on the
+gfx950 kernel rrt.hip.
 
 plan() keeps the reference's signature, return convention and its use of the global numpy RNG:
 the draws generateRandomNode (rrt.py:91-103) would make are read from a copy of np.random's
@@ -12,7 +12,7 @@ import math
 
 import numpy as np
 
-from . import batch
+from . import _lib, batch
 from .env import Map, Node
 from .planner import Planner
 
@@ -107,3 +107,72 @@ class RRTStar(RRT):
     @staticmethod
     def plan_batch(env: Map, starts, goals, rnd, sample_num: int, star: bool = True, **kw):
         return batch.rrt_batch(env, starts, goals, rnd, sample_num, star=star, **kw)
+
+
+class InformedRRT(RRTStar):
+    """Informed RRT* (informed_rrt.py:36-152): RRT* that keeps planning after the goal is connected,
+    sampling from the ellipse of paths no longer than the best one found."""
+
+    def __init__(self, start: tuple, goal: tuple, env: Map, max_dist: float = 0.5, sample_num: int = 1500,
+                 r: float = 12.0, goal_sample_rate: float = 0.05) -> None:
+        # informed_rrt.py:61 hands goal_sample_rate to RRTStar's `r` slot: the caller's rate is dropped
+        # and RRT's default 0.05 applies, whatever is passed
+        super().__init__(start, goal, env, max_dist, sample_num, goal_sample_rate)
+        self.r = r
+        self.c_best = float("inf")
+        self.c_min = math.hypot(self.goal.x - self.start.x, self.goal.y - self.start.y)
+
+    def __str__(self) -> str:
+        return "Informed RRT*"
+
+    def plan(self) -> tuple:
+        """(best_cost, best path goal->start, expand list of Node) or (inf, None, expand)
+        (informed_rrt.py:74-112).  The ellipse sampler's draw count has no bound: the stream starts at
+        4*sample_num+64 doubles and doubles while the kernel reports that it ran out (the re-run reads
+        the same draws, so the result does not depend on the stream's length)."""
+        state = np.random.get_state()
+        stride = 4 * int(self.sample_num) + 64
+        for _ in range(16):
+            rs = np.random.RandomState()
+            rs.set_state(state)
+            rnd = rs.random_sample(stride)
+            out = batch.informed_rrt_batch(self.env, [self.start.current], [self.goal.current], rnd[None],
+                                           self.sample_num, max_dist=self.max_dist, radius=self.r, delta=self.delta,
+                                           goal_sample_rate=self.goal_sample_rate)
+            st = int(out["status"][0])
+            if st != _lib.STATUS_CAP_OVERFLOW:
+                break
+            stride *= 2
+        n = int(out["n_nodes"][0])
+        draws = int(out["draws"][0])
+        if st not in (0, 1):
+            # (4: the reference's extractPath would never return; 3 here: no try lands in the map)
+            raise RuntimeError(f"Informed RRT* kernel status {st}")
+        if draws:
+            np.random.random_sample(draws)  # advance the global RNG exactly as the reference's loop does
+        xy = out["tree_xy"][0, :n].cpu().numpy()
+        g = out["tree_g"][0, :n].cpu().numpy()
+        par = out["tree_parent"][0, :n].cpu().numpy()
+        expand = []
+        for i in range(n):
+            cur = (float(xy[i, 0]), float(xy[i, 1]))
+            expand.append(Node(cur, (float(xy[par[i], 0]), float(xy[par[i], 1])), float(g[i]), 0))
+        # the start and goal keep the caller's coordinates (ints in the README examples)
+        expand[0] = self.start
+        if st == 1:
+            return float("inf"), None, expand
+        gs = int(out["goal_slot"][0])
+        self.goal.parent = expand[int(par[gs])].current
+        self.goal.g = float(g[gs])
+        expand[gs] = self.goal
+        plen = int(out["path_len"][0])
+        pts = out["path"][0, :plen].cpu().numpy()
+        path = [(float(x), float(y)) for x, y in pts]
+        path[0], path[-1] = self.goal.current, self.start.current
+        self.c_best = float(out["best_cost"][0])
+        return self.c_best, path, expand
+
+    @staticmethod
+    def plan_batch(env: Map, starts, goals, rnd, sample_num: int, **kw):
+        """Independent queries on one Map; rnd [nq, stride] random streams.  Device-tensor dict."""
+        return batch.informed_rrt_batch(env, starts, goals, rnd, sample_num, **kw)
