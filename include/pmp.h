@@ -100,6 +100,10 @@ int pmp_graph2d_batch(pmp_ctx* ctx, void* stream, int algo, const uint32_t* occ_
  *   path      [nq][path_cap] u32 cells start -> goal;  n_expanded = len(CLOSED) (distinct cells)
  *   expand    nullable [nq][expand_cap] u32 cells in first-insertion order of CLOSED
  *   counters  nullable [nq][4] i64 pushes, pops, expansions (incl. re-expansions), max heap size
+ * An endpoint outside the grid is not searched: status 1, cost inf, path_len 0; a start inside the grid
+ * is the one CLOSED cell (n_expanded 1, expand[0] = the start; 0 with the start outside) and the
+ * counters are 1, 1, n_expanded, 1.  (With the goal alone outside, the reference closes the start's
+ * whole component before it returns the same inf and [].)
  */
 int pmp_astar3d_batch(pmp_ctx* ctx, void* stream, const uint32_t* occ_bits, int per_query, int X, int Y, int Z,
                       int heuristic, const int32_t* start_xyz, const int32_t* goal_xyz, int nq, double* cost,

@@ -416,6 +416,23 @@ static inline int collide3(const uint8_t* occ, int X, int Y, int Z, int x1, int 
            occ3(occ, X, Y, Z, x1, y1, z1 + dz);
 }
 
+/* An endpoint outside the grid is not searched (include/pmp.h, pmp_astar3d_batch): status 1, cost inf,
+ * no path; a start inside the grid is the one CLOSED cell (n_expanded 1), and the counters are one
+ * push, one pop, that expansion, heap size 1.  Returns 1 when it has written that result. */
+static int endpoint_outside3(int X, int Y, int Z, const int32_t* s, const int32_t* g, double* cost_out,
+                             int32_t* path_len, int32_t* expand, int expand_cap, int32_t* n_expanded, int64_t* counters)
+{
+    const int s_in = s[0] >= 0 && s[1] >= 0 && s[2] >= 0 && s[0] < X && s[1] < Y && s[2] < Z;
+    const int g_in = g[0] >= 0 && g[1] >= 0 && g[2] >= 0 && g[0] < X && g[1] < Y && g[2] < Z;
+    if (s_in && g_in) return 0;
+    *path_len = 0;
+    *cost_out = INFINITY;
+    *n_expanded = s_in;
+    if (s_in && expand && expand_cap > 0) expand[0] = (s[0] * Y + s[1]) * Z + s[2];
+    if (counters) { counters[0] = 1; counters[1] = 1; counters[2] = s_in; counters[3] = 1; }
+    return 1;
+}
+
 /* heuristic: 0 euclidean = math.sqrt(dx**2+dy**2+dz**2) (graph_search_3d.py:40-50), 1 manhattan.
  * path: start -> goal.  expand: distinct CLOSED keys in first-insertion order.
  * Unreachable -> status 1 with cost = inf (a_star3d.py:77-78).
@@ -428,6 +445,7 @@ int oracle_graph3d(int algo, const uint8_t* occ, int X, int Y, int Z, int heuris
                    const int32_t* g, double* cost_out, int32_t* path, int path_cap, int32_t* path_len,
                    int32_t* expand, int expand_cap, int32_t* n_expanded, int64_t* counters)
 {
+    if (endpoint_outside3(X, Y, Z, s, g, cost_out, path_len, expand, expand_cap, n_expanded, counters)) return 1;
     const int64_t ncell = (int64_t)X * Y * Z;
     double* cg = (double*)malloc(sizeof(double) * (size_t)ncell);
     int32_t* cparent = (int32_t*)malloc(sizeof(int32_t) * (size_t)ncell);
@@ -588,6 +606,7 @@ int oracle_theta3d(int lazy, const uint8_t* occ, int X, int Y, int Z, int heuris
                    const int32_t* g, double* cost_out, int32_t* path, int path_cap, int32_t* path_len,
                    int32_t* expand, int expand_cap, int32_t* n_expanded, int64_t* counters)
 {
+    if (endpoint_outside3(X, Y, Z, s, g, cost_out, path_len, expand, expand_cap, n_expanded, counters)) return 1;
     const int64_t ncell = (int64_t)X * Y * Z, YZ = (int64_t)Y * Z;
     double* cg = (double*)malloc(sizeof(double) * (size_t)ncell);
     int32_t* cparent = (int32_t*)malloc(sizeof(int32_t) * (size_t)ncell);

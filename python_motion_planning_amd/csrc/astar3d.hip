@@ -427,6 +427,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(THETA == 0 ?
     }
 }
 
+// A query whose goal alone lies outside the grid leaves the search at once with n_expanded = 1: the
+// start is its one CLOSED cell.  This writes that cell to the query's expand row (a launch of its own,
+// only when expand records are asked for, so the search kernel's early exit stays a handful of stores).
+__global__ void a3_outside_goal_expand(const int32_t* __restrict__ s, const int32_t* __restrict__ g, int nq, int X, int Y,
+                                       int Z, uint32_t* __restrict__ expand, int expand_cap)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const int sx = s[3 * q], sy = s[3 * q + 1], sz = s[3 * q + 2];
+    const bool s_in = (unsigned)sx < (unsigned)X && (unsigned)sy < (unsigned)Y && (unsigned)sz < (unsigned)Z;
+    const bool g_in = (unsigned)g[3 * q] < (unsigned)X && (unsigned)g[3 * q + 1] < (unsigned)Y && (unsigned)g[3 * q + 2] < (unsigned)Z;
+    if (s_in && !g_in) expand[(size_t)q * expand_cap] = ((uint32_t)sx * (uint32_t)Y + (uint32_t)sy) * (uint32_t)Z + (uint32_t)sz;
+}
+
 // ---- longest-first schedule: counting sort of the queries by descending start-goal distance ----
 __device__ __forceinline__ int lpt3_key(const int32_t* s, const int32_t* g, int q)
 {
@@ -558,6 +572,11 @@ extern "C" int pmp_graph3d_batch(pmp_ctx* ctx, void* stream, int algo, const uin
                        algo == PMP_ALGO_GBFS ? 1 : 0, theta ? tpar : nullptr, theta ? tpar + (size_t)workers * ncell : nullptr,
                        ppar_cap, (const int32_t*)order, order ? ctx->astar_prio_n : 0);
     PMP_HIP_CHECK(ctx, hipGetLastError());
+    if (expand) {
+        hipLaunchKernelGGL(a3_outside_goal_expand, dim3((nq + 255) / 256), dim3(256), 0, s, start_xyz, goal_xyz, nq, X, Y, Z,
+                           expand, expand_cap);
+        PMP_HIP_CHECK(ctx, hipGetLastError());
+    }
     return PMP_OK;
 }
 
