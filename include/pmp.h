@@ -453,6 +453,38 @@ int pmp_track_step_batch(pmp_ctx* ctx, void* stream, int kind, const pmp_lp_para
                          const double* path_xy, const int32_t* path_off, int iters, double* u, int32_t* status,
                          int32_t* n_steps, double* hist_pose, int32_t* admm_iters);
 
+#define PMP_FOLLOW_PID 0
+#define PMP_FOLLOW_APF 1
+#define PMP_FOLLOW_RPP 2
+/* Settings of the path-following planners: PID's gains (local_planner/pid.py:35-44), APF's force
+ * weights and influence distance (apf.py:37-39), RPP's regulation settings (rpp.py:38-40).  Each
+ * kind reads its own group. */
+typedef struct {
+    double k_v_p, k_v_i, k_v_d, k_w_p, k_w_i, k_w_d, k_theta;
+    double zeta, eta, d_0;
+    double regulated_radius_min, scaling_dist, scaling_gain;
+} pmp_follow_params;
+
+/*
+ * Batched path-following plan iterations: `iters` iterations of PID.plan (pid.py:55-99, kind
+ * PMP_FOLLOW_PID), APF.plan (apf.py:50-95, PMP_FOLLOW_APF) or RPP.plan (rpp.py:51-99,
+ * PMP_FOLLOW_RPP) per agent, four agents per wave64 (one per 16-lane row): reachGoal,
+ * getLookaheadPoint, the rotate/move branch, the controller, Robot.kinematic.  The distance to the
+ * obstacle cells (APF.getRepulsiveForce, RPP.applyObstacleConstraint: a cdist over every obstacle in
+ * the reference) is a scan of the cells within d_0 / scaling_dist of the robot; cells outside the
+ * grid's box are free.  APF sums its repulsive terms in the scan's order, not list(set)'s.
+ * Arrays as pmp_dwa_step_batch (occ_bits may be NULL for PID; W, H <= 8192), plus
+ *   pid_state [na][4] f64 in/out   PID's e_v, i_v, e_w, i_w (start a planner with zeros); unused otherwise
+ *   hist_lookahead [na][iters][2] f64  nullable; the lookahead point of each step (RPP's lookahead_pts)
+ *   status   0 stepped, 1 goal reached, 4 the reference raises (getLookaheadPoint, or RPP's
+ *            1.0 / curvature with a curvature of +-0: that step is not taken or recorded)
+ */
+int pmp_follow_step_batch(pmp_ctx* ctx, void* stream, int kind, const uint32_t* occ_bits, int ox, int oy, int W, int H,
+                          const pmp_lp_params* lp, const pmp_follow_params* fp, int na, double* state,
+                          double* pid_state, const double* goal, const double* path_xy, const int32_t* path_off,
+                          int iters, double* u, int32_t* status, int32_t* n_steps, double* hist_pose,
+                          double* hist_lookahead);
+
 /* RRT / RRT* settings: Map size (utils/environment/env.py:92), inflation delta (sample_search.py:22),
  * max_dist, sample_num, goal_sample_rate (rrt.py:36-44), radius r (rrt_star.py:34-38). */
 typedef struct {

@@ -72,6 +72,8 @@ SIGNATURES = {
                                     _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "pmp_track_step_batch": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
                                   _vp]),
+    "pmp_follow_step_batch": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp,
+                                   _vp, _vp, _vp, _vp]),
     "pmp_totp3d_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
                               _vp, _i]),
 }
@@ -155,6 +157,27 @@ class TotpParams(ctypes.Structure):
 
 
 TRACK_LQR, TRACK_MPC = 0, 1
+
+
+class FollowParams(ctypes.Structure):
+    """pmp_follow_params == PID's gains (pid.py:35-44), APF's zeta / eta / d_0 (apf.py:37-39) and RPP's
+    regulated_radius_min / scaling_dist / scaling_gain (rpp.py:38-40); defaults are the reference's."""
+    _fields_ = [(n, ctypes.c_double) for n in (
+        "k_v_p", "k_v_i", "k_v_d", "k_w_p", "k_w_i", "k_w_d", "k_theta", "zeta", "eta", "d_0",
+        "regulated_radius_min", "scaling_dist", "scaling_gain")]
+    DEFAULTS = dict(k_v_p=1.0, k_v_i=0.1, k_v_d=0.1, k_w_p=1.0, k_w_i=0.1, k_w_d=0.1, k_theta=0.75, zeta=1.0, eta=1.0,
+                    d_0=1.0, regulated_radius_min=0.9, scaling_dist=0.6, scaling_gain=1.0)
+
+    @classmethod
+    def make(cls, **kw):
+        unknown = set(kw) - set(cls.DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown follow parameter(s): {sorted(unknown)}")
+        return cls(**{k: float(kw.get(k, d)) for k, d in cls.DEFAULTS.items()})
+
+
+FOLLOW_PID, FOLLOW_APF, FOLLOW_RPP = 0, 1, 2
+FOLLOW_KINDS = {"pid": FOLLOW_PID, "apf": FOLLOW_APF, "rpp": FOLLOW_RPP}
 
 STATUS_FOUND, STATUS_NO_PATH, STATUS_PATH_OVERFLOW, STATUS_CAP_OVERFLOW, STATUS_REF_RAISES = range(5)
 

@@ -338,6 +338,50 @@ def track_step_batch(kind: str, lp_params, state, goal, path_xy, path_off, iters
     return out
 
 
+def follow_step_batch(kind: str, grid, lp_params, follow_params, state, goal, path_xy, path_off, iters: int = 1,
+                      pid_state=None, want_hist: bool = False, want_lookahead: bool = False):
+    """Batched PID.plan / APF.plan / RPP.plan iterations (pid.py:55-99, apf.py:50-95, rpp.py:51-99) on
+    the gfx950 kernel follow.hip, kind "pid", "apf" or "rpp".
+
+    grid: (ox, oy, occ[W, H]) from obstacle_grid() (or with occ already a device bit tensor plus (W, H));
+    may be None for PID, which reads no obstacles.  lp_params: _lib.LPParams; follow_params: _lib.FollowParams.
+    state [na,5] f64 device tensor (updated in place); pid_state [na,4] f64 device tensor (PID: e_v, i_v,
+    e_w, i_w, in place).  Returns dict of device tensors (u, status, n_steps, optional hist_pose
+    [na,iters,3] and lookahead [na,iters,2])."""
+    torch = _lib.device_check()
+    L = _lib.load_library()
+    ctx = _lib.context()
+    k = _lib.FOLLOW_KINDS[kind]
+    occ_bits, ox, oy, W, H = None, 0, 0, 0, 0
+    if grid is not None:
+        ox, oy, occ = grid[:3]
+        if isinstance(occ, np.ndarray):
+            W, H = occ.shape
+            occ_bits = occ_bits_device(occ, torch)
+        else:
+            occ_bits, (W, H) = occ, grid[3]
+    elif k != _lib.FOLLOW_PID:
+        raise ValueError(f"{kind} needs the obstacle grid")
+    if k == _lib.FOLLOW_PID and pid_state is None:
+        raise ValueError("PID needs the carried pid_state tensor [na, 4]")
+    na = int(state.shape[0])
+    goal = _dev(torch, goal, torch.float64).reshape(-1, 3)
+    path_xy = _dev(torch, path_xy, torch.float64).reshape(-1, 2)
+    path_off = _dev(torch, path_off, torch.int32)
+    out = dict(u=torch.empty((na, 2), dtype=torch.float64, device="cuda"),
+               status=torch.empty(na, dtype=torch.int32, device="cuda"),
+               n_steps=torch.empty(na, dtype=torch.int32, device="cuda"))
+    out["hist_pose"] = torch.zeros((na, iters, 3), dtype=torch.float64, device="cuda") if want_hist else None
+    out["lookahead"] = torch.zeros((na, iters, 2), dtype=torch.float64, device="cuda") if want_lookahead else None
+    rc = L.pmp_follow_step_batch(ctx, _lib.stream_ptr(), k, _lib.ptr(occ_bits), int(ox), int(oy), int(W), int(H),
+                                 ctypes.byref(lp_params), ctypes.byref(follow_params), na, state.data_ptr(),
+                                 _lib.ptr(pid_state), goal.data_ptr(), path_xy.data_ptr(), path_off.data_ptr(),
+                                 int(iters), out["u"].data_ptr(), out["status"].data_ptr(), out["n_steps"].data_ptr(),
+                                 _lib.ptr(out["hist_pose"]), _lib.ptr(out["lookahead"]))
+    _lib.check(ctx, rc, "pmp_follow_step_batch")
+    return out
+
+
 def dstar2d_batch(occ, starts, goals, path_cap: int | None = None, max_process: int = 0):
     """Batched DStar.plan (d_star.py:75-156) on one Grid.  occ uint8 [W, H] (x-major).
     Returns dict of device tensors: cost, path_len, path [nq, path_cap] (cells x*H+y, start -> goal),

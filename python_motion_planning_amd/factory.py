@@ -5,6 +5,8 @@ substituted)."""
 from __future__ import annotations
 
 _SEARCH_OUT_OF_SCOPE = {"jps", "voronoi", "s_theta_star", "anya", "rrt_connect", "aco", "pso"}
+# PID / APF / RPP exist as classes (local_planner.PID, APF, RPP); like "jps", their factory names keep
+# raising
 _CONTROL_OUT_OF_SCOPE = {"pid", "apf", "rpp"}
 
 
@@ -38,5 +40,6 @@ class ControlFactory(object):
                 raise NotImplementedError(f"{planner_name} is not implemented yet in python_motion_planning_amd")
             return cls(**config)
         if planner_name in _CONTROL_OUT_OF_SCOPE:
-            raise NotImplementedError(f"{planner_name} is outside the accelerated hot path of python_motion_planning_amd")
+            raise NotImplementedError(f"{planner_name} is not a ControlFactory name of python_motion_planning_amd; "
+                                      f"construct python_motion_planning_amd.{planner_name.upper()} directly")
         raise ValueError("The `planner_name` must be set correctly.")

@@ -1,8 +1,9 @@
-"""Local planners: drop-in Robot / LocalPlanner / DWA (local_planner/ and utils/agent/ of the reference).
+"""Local planners: drop-in Robot / LocalPlanner / DWA / LQR / MPC / PID / APF / RPP (local_planner/
+and utils/agent/ of the reference).
 
 plan() keeps the reference's return conventions; the per-iteration control step runs in the
-gfx950 kernels (dwa.hip).  step() is one iteration of the reference's plan loop; plan_batch()
-runs many independent agents at once.
+gfx950 kernels (dwa.hip, track.hip, follow.hip).  step() is one iteration of the reference's plan
+loop; the batch.*_step_batch functions run many independent agents at once.
 """
 from __future__ import annotations
 
@@ -222,6 +223,136 @@ class _Tracker(LocalPlanner):
 
     def run(self):
         return self.plan()
+
+
+class _Follower(LocalPlanner):
+    """Shared plan loop of PID / APF / RPP (pid.py:55-99, apf.py:50-95, rpp.py:51-99) on the gfx950
+    kernel follow.hip.  The controller settings are read from the planner's attributes at each call."""
+
+    KIND = "pid"
+    RAISES = (IndexError, "getLookaheadPoint failed (reference raises)")
+
+    def _set_global_path(self, start, goal, env) -> None:
+        self.g_planner = {"planner_name": "a_star", "start": (start[0], start[1]), "goal": (goal[0], goal[1]),
+                          "env": env}
+        self.path = self.g_path[::-1]
+
+    def _follow_params(self):
+        names = _lib.FollowParams.DEFAULTS
+        return _lib.FollowParams.make(**{k: getattr(self, k) for k in names if hasattr(self, k)})
+
+    def _run(self, iters: int):
+        """-> (status, lookahead points of the steps taken)."""
+        torch = _lib.device_check()
+        grid = None
+        if self.KIND != "pid":
+            if not self.obstacles:  # the reference's cdist / np.min over an empty obstacle array
+                raise ValueError("%s needs at least one obstacle cell" % type(self).__name__)
+            grid = batch.obstacle_grid(self.obstacles)
+        r = self.robot
+        state = torch.tensor([[r.px, r.py, r.theta, r.v, r.w]], dtype=torch.float64, device="cuda")
+        pid = None
+        if self.KIND == "pid":
+            pid = torch.tensor([[self.e_v, self.i_v, self.e_w, self.i_w]], dtype=torch.float64, device="cuda")
+        xy, off = batch.pack_paths([np.asarray(self.path, np.float64)])
+        out = batch.follow_step_batch(self.KIND, grid, self._lp_params(), self._follow_params(), state,
+                                      np.array([self.goal], np.float64), xy, off, iters=iters, pid_state=pid,
+                                      want_hist=True, want_lookahead=self.KIND == "rpp")
+        n = int(out["n_steps"][0])
+        st = int(out["status"][0])
+        for p in out["hist_pose"][0, :n].cpu().numpy():
+            r.history_pose.append((float(p[0]), float(p[1]), float(p[2])))
+        r.px, r.py, r.theta, r.v, r.w = (float(v) for v in state[0].cpu().numpy())
+        if pid is not None:
+            self.e_v, self.i_v, self.e_w, self.i_w = (float(v) for v in pid[0].cpu().numpy())
+        pts = []
+        if out["lookahead"] is not None:
+            pts = [(float(p[0]), float(p[1])) for p in out["lookahead"][0, :n].cpu().numpy()]
+        return st, pts
+
+    def step(self):
+        """One iteration of the plan loop.  Returns 'reached' or 'stepped'; raises where the reference does."""
+        st, _ = self._run(1)
+        if st == _lib.STATUS_REF_RAISES:
+            raise self.RAISES[0](self.RAISES[1])
+        return "reached" if st == 1 else "stepped"
+
+    def plan(self):
+        """(True, history_pose) or (False, None)."""
+        st, _ = self._run(int(self.params["MAX_ITERATION"]))
+        if st == 1:
+            return True, self.robot.history_pose
+        if st == _lib.STATUS_REF_RAISES:
+            raise self.RAISES[0](self.RAISES[1])
+        return False, None
+
+    def run(self):
+        return self.plan()
+
+
+class PID(_Follower):
+    """PID path tracking (local_planner/pid.py:14-158).  The integrators e_v, i_v, e_w, i_w carry over
+    between calls, as the reference's attributes do."""
+
+    KIND = "pid"
+
+    def __init__(self, start: tuple, goal: tuple, env: Env, heuristic_type: str = "euclidean",
+                 k_v_p: float = 1.00, k_v_i: float = 0.10, k_v_d: float = 0.10,
+                 k_w_p: float = 1.00, k_w_i: float = 0.10, k_w_d: float = 0.10,
+                 k_theta: float = 0.75, **params) -> None:
+        super().__init__(start, goal, env, heuristic_type, MIN_LOOKAHEAD_DIST=0.75, **params)
+        self.e_w, self.i_w = 0.0, 0.0
+        self.e_v, self.i_v = 0.0, 0.0
+        self.k_v_p, self.k_v_i, self.k_v_d = k_v_p, k_v_i, k_v_d
+        self.k_w_p, self.k_w_i, self.k_w_d = k_w_p, k_w_i, k_w_d
+        self.k_theta = k_theta
+        self._set_global_path(start, goal, env)
+
+    def __str__(self) -> str:
+        return "PID Planner"
+
+
+class APF(_Follower):
+    """Artificial Potential Field (local_planner/apf.py:14-144); the repulsive force scans the
+    obstacle cells within d_0 of the robot."""
+
+    KIND = "apf"
+
+    def __init__(self, start: tuple, goal: tuple, env: Env, heuristic_type: str = "euclidean", **params) -> None:
+        super().__init__(start, goal, env, heuristic_type, **params)
+        self.zeta = 1.0
+        self.eta = 1.0
+        self.d_0 = 1.0
+        self._set_global_path(start, goal, env)
+
+    def __str__(self) -> str:
+        return "Artificial Potential Field(APF)"
+
+
+class RPP(_Follower):
+    """Regulated Pure Pursuit (local_planner/rpp.py:15-147).  plan() also returns the lookahead points."""
+
+    KIND = "rpp"
+    RAISES = (ZeroDivisionError, "float division by zero")  # 1.0 / curvature (rpp.py:125)
+
+    def __init__(self, start: tuple, goal: tuple, env: Env, heuristic_type: str = "euclidean", **params) -> None:
+        super().__init__(start, goal, env, heuristic_type, **params)
+        self.regulated_radius_min = 0.9
+        self.scaling_dist = 0.6
+        self.scaling_gain = 1.0
+        self._set_global_path(start, goal, env)
+
+    def __str__(self) -> str:
+        return "Regulated Pure Pursuit (RPP)"
+
+    def plan(self):
+        """(True, history_pose, lookahead_pts) or (False, None, None)."""
+        st, pts = self._run(int(self.params["MAX_ITERATION"]))
+        if st == 1:
+            return True, self.robot.history_pose, pts
+        if st == _lib.STATUS_REF_RAISES:
+            raise self.RAISES[0](self.RAISES[1])
+        return False, None, None
 
 
 class LQR(_Tracker):
