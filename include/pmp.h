@@ -558,6 +558,47 @@ int pmp_informed_rrt_batch(pmp_ctx* ctx, void* stream, const pmp_rrt_params* p, 
                            int32_t* goal_slot, int32_t* path_len, double* path_xy, int path_cap, int64_t* draws,
                            int32_t* status, int64_t* counters);
 
+/*
+ * Batched RRT-Connect.  Replaces RRTConnect.plan, extractPath and getExpand
+ * (global_planner/sample_search/rrt_connect.py:42-147) with RRT.generateRandomNode / getNearest
+ * (rrt.py:92-130) and SampleSearcher.isCollision (sample_search.py:27-135): two trees, one rooted at the
+ * start and one at the goal; each iteration extends the forward tree towards a sample, the backward tree
+ * towards the new node and then greedily on towards it, and the smaller tree becomes the forward one.
+ * One 64-lane wave per query, four queries per workgroup; queries never interact.  All arrays are device
+ * pointers; those not listed are pmp_rrt_batch's.
+ *   p                     pmp_rrt_params; radius and star are ignored
+ *   rnd [nq][rnd_stride]  the np.random double stream: 1 or 3 doubles per iteration, so 3*sample_num
+ *                         always suffice (there is no `in sample_list` skip: every iteration draws)
+ *   tree_xy [nq][2][tree_cap][2], tree_g [nq][2][tree_cap], tree_parent [nq][2][tree_cap]
+ *                         out: both sample lists in dict order.  Tree 0 is rooted at the start, tree 1 at
+ *                         the goal; parents are indices into their own tree, a root's parent is 0.  A sample
+ *                         at distance 0 from its nearest node (the goal, sampled while tree 1 is forward)
+ *                         replaces that node in place, as the dict does: its parent becomes itself
+ *   n_nodes [nq][2]       out: len() of each tree
+ *   forward [nq]          out: which tree was sample_list_f when the plan ended (getExpand interleaves it first)
+ *   boundary [nq][2]      out: the meeting node's index in each tree, -1 when the trees never met
+ *   cost [nq]             out: the meeting node's g in tree 0 + its g in tree 1, 0 when not found
+ *   path_len [nq], path_xy [nq][path_cap][2]   out: extractPath, start -> meeting node -> goal (the meeting
+ *                         node once)
+ *   iters [nq]            out: iterations run, the one that returned included
+ *   draws [nq] i64        out: doubles consumed from rnd (advance the caller's RNG by this many)
+ *   status [nq]           0 found, 1 not found (returns (0, None, None)), 2 path_cap overflow (cost, path_len
+ *                         and the trees are complete), 3 tree_cap overflow in either tree (or the stream
+ *                         ended), 4 a parent walk did not reach its root (the reference never returns)
+ *   counters [nq][4] i64  nullable: iterations, nodes scanned by the nearest passes, isCollision calls,
+ *                         greedy steps
+ * A steered node that lands exactly on a different existing node is appended, not merged (the reference's
+ * dict would replace that entry; the chance is about 2^-50 per insert).
+ */
+int pmp_rrt_connect_batch(pmp_ctx* ctx, void* stream, const pmp_rrt_params* p, const double* rect, int nr,
+                          const double* circ, int nc, const double* bnd, int nb, const double* start_xy,
+                          const double* goal_xy, int nq, const double* rnd, int64_t rnd_stride, int tree_cap,
+                          double* tree_xy, double* tree_g, int32_t* tree_parent, int32_t* n_nodes, int32_t* forward,
+                          int32_t* boundary, double* cost, int32_t* path_len, double* path_xy, int path_cap,
+                          int32_t* iters, int64_t* draws, int32_t* status, int64_t* counters);
+/* Nodes of each tree pmp_rrt_connect_batch keeps in LDS; larger trees continue in the HBM arrays. */
+int pmp_rrt_connect_lds_nodes(void);
+
 /* TrajectoryConstraints (trajectory/trajectory_base.py:30-45) and TimeOptimalTrajectory3D's
  * path_resolution (trajectory/time_optimal_trajectory.py:17-29) */
 typedef struct {

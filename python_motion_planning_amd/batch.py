@@ -616,6 +616,58 @@ def informed_rrt_batch(env, starts, goals, rnd, sample_num: int, max_dist: float
     return out
 
 
+RRT_CONNECT_DEFAULT_CAP = 2048
+
+
+def rrt_connect_lds_nodes() -> int:
+    """Nodes of each tree rrt_connect.hip keeps in LDS (larger trees continue in HBM)."""
+    return int(_lib.load_library().pmp_rrt_connect_lds_nodes())
+
+
+def rrt_connect_batch(env, starts, goals, rnd, sample_num: int, max_dist: float = 0.5, goal_sample_rate: float = 0.05,
+                      delta: float = 0.5, cap: int | None = None, path_cap: int | None = None, counters: bool = False):
+    """Batched RRT-Connect plans (rrt_connect.py:42-147) on one Map.
+    rnd: [nq, stride] f64 random streams (RandomState.random_sample order; 3*sample_num per query suffice).
+    cap: nodes per tree, default 2048 -- the reference's runs on the README map need up to 150 and C3 with
+    max_dist 0.5 about 1,100.  An iteration adds one node plus its greedy steps, so sample_num does not
+    bound a tree: a query that outgrows cap reports status 3 (re-run it with a larger one; RRTConnect.plan
+    doubles it).  Memory is nq x 2 x cap x 28 B.  path_cap defaults to 2 * cap, which holds any path.
+    Returns dict of device tensors: tree_xy [nq,2,cap,2], tree_g, tree_parent [nq,2,cap] (tree 0 rooted at
+    the start, tree 1 at the goal), n_nodes [nq,2], forward, boundary [nq,2], cost, path_len, path
+    [nq,path_cap,2] (start -> goal), iters, draws, status."""
+    torch = _lib.device_check()
+    L = _lib.load_library()
+    ctx = _lib.context()
+    rect, circ, bnd = map_arrays(env, torch)
+    s = _dev(torch, starts, torch.float64).reshape(-1, 2)
+    g = _dev(torch, goals, torch.float64).reshape(-1, 2)
+    nq = int(s.shape[0])
+    rnd = _dev(torch, rnd, torch.float64).reshape(nq, -1)
+    cap = RRT_CONNECT_DEFAULT_CAP if cap is None else int(cap)
+    path_cap = 2 * cap if path_cap is None else int(path_cap)
+    f64 = dict(dtype=torch.float64, device="cuda")
+    i32 = dict(dtype=torch.int32, device="cuda")
+    out = dict(tree_xy=torch.empty((nq, 2, cap, 2), **f64), tree_g=torch.empty((nq, 2, cap), **f64),
+               tree_parent=torch.empty((nq, 2, cap), **i32), n_nodes=torch.empty((nq, 2), **i32),
+               forward=torch.empty(nq, **i32), boundary=torch.empty((nq, 2), **i32), cost=torch.empty(nq, **f64),
+               path_len=torch.empty(nq, **i32), path=torch.empty((nq, max(path_cap, 1), 2), **f64),
+               iters=torch.empty(nq, **i32), draws=torch.empty(nq, dtype=torch.int64, device="cuda"),
+               status=torch.empty(nq, **i32),
+               counters=torch.zeros((nq, 4), dtype=torch.int64, device="cuda") if counters else None)
+    P = _lib.RRTParams(float(env.x_range), float(env.y_range), float(delta), float(max_dist), 0.0,
+                       float(goal_sample_rate), int(sample_num), 0)
+    rc = L.pmp_rrt_connect_batch(ctx, _lib.stream_ptr(), ctypes.byref(P), rect.data_ptr(), int(rect.shape[0]),
+                                 circ.data_ptr(), int(circ.shape[0]), bnd.data_ptr(), int(bnd.shape[0]),
+                                 s.data_ptr(), g.data_ptr(), nq, rnd.data_ptr(), int(rnd.shape[1]), cap,
+                                 out["tree_xy"].data_ptr(), out["tree_g"].data_ptr(), out["tree_parent"].data_ptr(),
+                                 out["n_nodes"].data_ptr(), out["forward"].data_ptr(), out["boundary"].data_ptr(),
+                                 out["cost"].data_ptr(), out["path_len"].data_ptr(), out["path"].data_ptr(), path_cap,
+                                 out["iters"].data_ptr(), out["draws"].data_ptr(), out["status"].data_ptr(),
+                                 _lib.ptr(out["counters"]))
+    _lib.check(ctx, rc, "pmp_rrt_connect_batch")
+    return out
+
+
 def astar3d_batch(occ, starts, goals, heuristic: str = "euclidean", path_cap: int | None = None,
                   expand_cap: int = 0, counters: bool = False, algo: str = "astar"):
     """Batched AStar3D.plan (a_star3d.py:33-106); algo "dijkstra" / "gbfs" run Dijkstra3D.plan

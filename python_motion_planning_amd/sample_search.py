@@ -1,5 +1,5 @@
 """Sample-search planners: drop-in RRT / RRTStar / InformedRRT (global_planner/sample_search/) on the
-gfx950 kernel rrt.hip.
+gfx950 kernel rrt.hip, and RRTConnect on rrt_connect.hip.
 
 plan() keeps the reference's signature, return convention and its use of the global numpy RNG:
 the draws generateRandomNode (rrt.py:91-103) would make are read from a copy of np.random's
@@ -176,3 +176,71 @@ class InformedRRT(RRTStar):
     def plan_batch(env: Map, starts, goals, rnd, sample_num: int, **kw):
         """Independent queries on one Map; rnd [nq, stride] random streams.  Device-tensor dict."""
         return batch.informed_rrt_batch(env, starts, goals, rnd, sample_num, **kw)
+
+
+class RRTConnect(RRT):
+    """RRT-Connect (rrt_connect.py:13-147): a tree from the start and one from the goal, each iteration
+    extending one towards a sample and the other greedily towards the new node until they meet."""
+
+    def __init__(self, start: tuple, goal: tuple, env: Map, max_dist: float = 0.5, sample_num: int = 10000,
+                 goal_sample_rate: float = 0.05) -> None:
+        super().__init__(start, goal, env, max_dist, sample_num, goal_sample_rate)
+
+    def __str__(self) -> str:
+        return "RRT-Connect"
+
+    def plan(self) -> tuple:
+        """(cost, path start->goal, expand list of Node) or (0, None, None) (rrt_connect.py:42-90).
+        expand is getExpand's interleave (rrt_connect.py:128-147): sample_list_f and sample_list_b of the
+        last iteration, index by index, the forward one first.  The trees start at batch.rrt_connect_batch's
+        default capacity, which doubles while the kernel reports that a tree outgrew it (the re-run reads
+        the same draws, so the result does not depend on the capacity)."""
+        rnd = random_stream(self.sample_num)
+        cap = batch.RRT_CONNECT_DEFAULT_CAP
+        for _ in range(16):
+            out = batch.rrt_connect_batch(self.env, [self.start.current], [self.goal.current], rnd[None],
+                                          self.sample_num, max_dist=self.max_dist,
+                                          goal_sample_rate=self.goal_sample_rate, delta=self.delta, cap=cap)
+            st = int(out["status"][0])
+            if st != _lib.STATUS_CAP_OVERFLOW:
+                break
+            cap *= 2
+        if st not in (0, 1):
+            # (4: the reference's extractPath would never return)
+            raise RuntimeError(f"RRT-Connect kernel status {st}")
+        draws = int(out["draws"][0])
+        if draws:
+            np.random.random_sample(draws)  # advance the global RNG exactly as the reference's loop does
+        if st == 1:
+            return 0, None, None
+        counts = out["n_nodes"][0].cpu().numpy()
+        roots = (self.start, self.goal)
+        trees = []
+        for t in (0, 1):
+            n = int(counts[t])
+            xy = out["tree_xy"][0, t, :n].cpu().numpy()
+            g = out["tree_g"][0, t, :n].cpu().numpy()
+            par = out["tree_parent"][0, t, :n].cpu().numpy()
+            nodes = [Node((float(xy[i, 0]), float(xy[i, 1])), (float(xy[par[i], 0]), float(xy[par[i], 1])),
+                          float(g[i]), 0) for i in range(n)]
+            # the roots keep the caller's coordinates (ints in the README examples)
+            nodes[0] = roots[t]
+            trees.append(nodes)
+        fw = int(out["forward"][0])
+        f, b = trees[fw], trees[1 - fw]
+        expand = []
+        for k in range(max(len(f), len(b))):
+            if k < len(f):
+                expand.append(f[k])
+            if k < len(b):
+                expand.append(b[k])
+        plen = int(out["path_len"][0])
+        pts = out["path"][0, :plen].cpu().numpy()
+        path = [(float(x), float(y)) for x, y in pts]
+        path[0], path[-1] = self.start.current, self.goal.current
+        return float(out["cost"][0]), path, expand
+
+    @staticmethod
+    def plan_batch(env: Map, starts, goals, rnd, sample_num: int, **kw):
+        """Independent queries on one Map; rnd [nq, stride] random streams.  Device-tensor dict."""
+        return batch.rrt_connect_batch(env, starts, goals, rnd, sample_num, **kw)
