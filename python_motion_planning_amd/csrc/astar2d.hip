@@ -28,6 +28,7 @@
 // Both operations are written for a low instruction count: the kernel is issue-bound (one wave per
 // query, a few waves per SIMD), so every instruction on the heap path costs wall time.
 #include "pmp_internal.h"
+#include "astar2d_entry.h"
 #include "grid2d.h"
 
 // Diagnostic build only (make stamps -> libpmp_hip_stamps.so): per-query cycle sums of the
@@ -43,53 +44,12 @@ namespace {
 constexpr int kMaxDim = 8192;
 constexpr double kSqrt2 = 1.4142135623730951;  // math.sqrt(2) == math.hypot(1, 1)
 
-// motions in the order of env.py:52-55: (-1,0),(-1,1),(0,1),(1,1),(1,0),(1,-1),(0,-1),(-1,-1),
-// as 2-bit fields of (m + 1)
-constexpr uint32_t kMx1 = 0x1A90u, kMy1 = 0x01A9u;
-__device__ __forceinline__ int mot_x(int d) { return (int)((kMx1 >> (2 * d)) & 3u) - 1; }
-__device__ __forceinline__ int mot_y(int d) { return (int)((kMy1 >> (2 * d)) & 3u) - 1; }
-
-// HEUR (a template parameter, so key computations carry no runtime branch): bits 0-1 = the
-// heuristic -- 0 euclidean, 1 manhattan (GraphSearcher.h, graph_search.py:41-44), 2 zero (Dijkstra's
-// node_n.h = 0, dijkstra.py:74); bit 2 = the Theta* entry layout: a 5-bit code instead of the 4-bit
-// dir (code 16 + dir = "path 2": the parent is the pusher's own parent, theta_star.py:104-108) and a
-// 13-bit dy field (H <= 4096).
-constexpr int kThetaLayout = 4;
-template <int HEUR> constexpr int hkind() { return HEUR & 3; }
-template <int HEUR> constexpr int dbits() { return (HEUR & kThetaLayout) ? 5 : 4; }
-template <int HEUR>
-__device__ __forceinline__ uint32_t pack_cm(int dx, int dy, int dir)
-{
-    constexpr int S = dbits<HEUR>();
-    return ((uint32_t)dx << 18) | (((uint32_t)dy & ((1u << (18 - S)) - 1u)) << S) | (uint32_t)dir;
-}
-template <int HEUR> __device__ __forceinline__ int cm_dx(uint32_t cm) { return (int)cm >> 18; }
-template <int HEUR> __device__ __forceinline__ int cm_dy(uint32_t cm) { return (int)(cm << 14) >> (14 + dbits<HEUR>()); }
-template <int HEUR> __device__ __forceinline__ int cm_dir(uint32_t cm) { return (int)(cm & ((1u << dbits<HEUR>()) - 1u)); }
-
-// The order key of h.
-template <int HEUR>
-__device__ __forceinline__ uint32_t hkey(uint32_t cm)
-{
-    if (hkind<HEUR>() == 2) return 0u;
-    const int dx = cm_dx<HEUR>(cm), dy = cm_dy<HEUR>(cm);
-    if (hkind<HEUR>() == 1) return (uint32_t)(abs(dx) + abs(dy));
-    return (uint32_t)(__mul24(dx, dx) + __mul24(dy, dy));
-}
+// h from its order key (astar2d_entry.h)
 template <int HEUR>
 __device__ __forceinline__ double h_of_key(uint32_t hk)
 {
     return hkind<HEUR>() == 2 ? 0.0 : (hkind<HEUR>() == 1 ? (double)hk : __dsqrt_rn((double)hk));
 }
-
-// Node.__lt__ (node.py:51-54) -- evaluated without short-circuit branches
-__device__ __forceinline__ bool key_lt(double fa, uint32_t ka, double fb, uint32_t kb)
-{
-    return (fa < fb) | ((fa == fb) & (ka < kb));
-}
-
-typedef __attribute__((address_space(3))) double lds_f64;
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
 
 // Direction bits.  For every node p with two children the heap also keeps CPython _siftup's child
 // choice bit(p) = !(heap[2p+1] < heap[2p+2]) (Lib/heapq.py: "if rightpos < endpos and not
@@ -113,14 +73,6 @@ struct Heap {
     __amdgpu_buffer_rsrc_t spill;  // HBM entries {f lo, f hi, cm, 0} for positions >= lds_cap
     int cap;
 };
-
-// per lane: bit `lane` of mask ? a : b
-__device__ __forceinline__ uint32_t sel_lanes(uint64_t mask, uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_cndmask_b32_e64 %0, %2, %1, %3" : "=v"(r) : "v"(a), "v"(b), "s"(mask));
-    return r;
-}
 
 // Entry load in two phases, so a round of several loads is issued before any value is used.
 // SPILL = false: every position touched is < cap (pure ds_read code).  SPILL: both an LDS read
@@ -199,13 +151,6 @@ __device__ __forceinline__ size_t hb_word(int t, uint32_t R)
 {
     const size_t base = (size_t)1 << (5 * t);
     return (base - 32768u) / 31u + (size_t)(R - (uint32_t)base);
-}
-
-// LDS atomic masked OR: word = (word & ~mask) | val, no return value (nothing waits on it).  LDS
-// operations of one wave complete in order, so later ds_reads of the word see it.
-__device__ __forceinline__ void ds_mskor(lds_u32* w, uint32_t mask, uint32_t val)
-{
-    asm volatile("ds_mskor_b32 %0, %1, %2" ::"v"((uint32_t)(uintptr_t)w), "v"(mask), "v"(val) : "memory");
 }
 
 // Block coordinates of a level: tier t = level / 5, r = level - 5t, mr = 2^r - 1 and the LDS word
@@ -296,14 +241,6 @@ __device__ __forceinline__ uint32_t walk5(uint32_t w2)
         : "s"(w2)
         : "scc");
     return pr;
-}
-
-__device__ __forceinline__ void wave_sync_mem()
-{
-    // Orders this wave's LDS and HBM accesses across its lanes.  A wave's memory operations are
-    // performed in order, so wavefront scope needs no s_waitcnt (LLVM AMDGPU memory model): this
-    // is a compiler barrier only and never stalls on outstanding HBM stores.
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 }
 
 // heappop on a heap of n (> 0, already decremented) entries whose old last element sits at
@@ -958,38 +895,6 @@ __global__ __launch_bounds__(64) void astar2d_kernel(
     span_end(span);
 }
 
-// ---- longest-first schedule: counting sort of the queries by descending start-goal distance ----
-__device__ __forceinline__ int lpt_key(const int32_t* s, const int32_t* g, int q)
-{
-    const double dx = (double)s[2 * q] - g[2 * q], dy = (double)s[2 * q + 1] - g[2 * q + 1];
-    const double d = __dsqrt_rn(dx * dx + dy * dy);  // expansions grow ~ with distance^2
-    return d < 2147483647.0 ? (int)d : 2147483647;  // callers clamp to the histogram's last bin
-}
-
-__global__ void lpt_hist(const int32_t* s, const int32_t* g, int nq, int nb, int* hist)
-{
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < nq) atomicAdd(&hist[min(lpt_key(s, g, q), nb - 1)], 1);
-}
-
-// offsets[k] = number of queries with a larger key (descending order); one thread, nb <= 16384
-__global__ void lpt_scan(int nb, int* hist)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int run = 0;
-    for (int k = nb - 1; k >= 0; k--) {
-        const int c = hist[k];
-        hist[k] = run;
-        run += c;
-    }
-}
-
-__global__ void lpt_scatter(const int32_t* s, const int32_t* g, int nq, int nb, int* offs, int32_t* order)
-{
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < nq) order[atomicAdd(&offs[min(lpt_key(s, g, q), nb - 1)], 1)] = q;
-}
-
 int default_workers() { return 256 * 4; }
 int default_lds_cap(int workers_per_cu)
 {
@@ -1017,22 +922,6 @@ int default_heap_cap(int W, int H)
 }
 // per-context scratch budget: workers are reduced to fit (heap spill + cell state + G per worker)
 constexpr size_t kScratchBudget = (size_t)64 << 30;
-
-// longest-first order of a batch in the context's SCR_PDIR scratch (counting sort, descending
-// start-goal distance)
-int lpt_order2d(pmp_ctx* ctx, hipStream_t s, const int32_t* start_xy, const int32_t* goal_xy, int nq, int W, int H,
-                int32_t** order)
-{
-    const int nb = (int)ceil(sqrt((double)W * W + (double)H * H)) + 1;
-    int* hist = (int*)pmp_scratch(ctx, SCR_PDIR, sizeof(int) * ((size_t)nb + (size_t)nq));
-    if (!hist) return PMP_ENOMEM;
-    *order = hist + nb;
-    PMP_HIP_CHECK(ctx, hipMemsetAsync(hist, 0, sizeof(int) * (size_t)nb, s));
-    hipLaunchKernelGGL(lpt_hist, dim3((nq + 255) / 256), dim3(256), 0, s, start_xy, goal_xy, nq, nb, hist);
-    hipLaunchKernelGGL(lpt_scan, dim3(1), dim3(64), 0, s, nb, hist);
-    hipLaunchKernelGGL(lpt_scatter, dim3((nq + 255) / 256), dim3(256), 0, s, start_xy, goal_xy, nq, nb, hist, *order);
-    return PMP_OK;
-}
 
 }  // namespace
 
@@ -1200,6 +1089,7 @@ extern "C" int pmp_graph2d_batch(pmp_ctx* ctx, void* stream, int algo, const uin
     }
     const size_t ncell = (size_t)W * H;
     const size_t cst_words = ((ncell + 7) / 8 + 3) & ~(size_t)3;
+    const int ext[2] = {W, H};  // for the longest-first pre-pass (lpt_order.hip)
     // one-query-per-wave launch geometry: the reservation's, or on a multi-query reservation this
     // engine's defaults for the batch (with the heap capacity asked for, or this engine's default: not the multi-query limit)
     int heap_cap = ctx->astar_heap_cap;
@@ -1249,10 +1139,8 @@ extern "C" int pmp_graph2d_batch(pmp_ctx* ctx, void* stream, int algo, const uin
         hipStream_t s = (hipStream_t)stream;
         PMP_HIP_CHECK(ctx, hipMemsetAsync(queue, 0, 16, s));
         int32_t* order = nullptr;
-        if (ctx->astar_lpt && nq > groups) {
-            const int rc = lpt_order2d(ctx, s, start_xy, goal_xy, nq, W, H, &order);
-            if (rc) return rc;
-        }
+        const int rc = pmp_lpt_order(ctx, s, 2, start_xy, goal_xy, nq, ext, groups, &order);
+        if (rc) return rc;
         return pmp_astar2d_mq_launch(ctx, s, algo, occ_bits, W, H, heuristic, start_xy, goal_xy, order, nq, cost,
                                      path_len, path, path_cap, n_expanded, expand, expand_cap, counters, status, queue);
     }
@@ -1274,8 +1162,8 @@ extern "C" int pmp_graph2d_batch(pmp_ctx* ctx, void* stream, int algo, const uin
     const size_t lds = (size_t)kBitsLdsBytes + (size_t)lds_cap * 12 + (ldsg ? ldsg_bytes(ncell) : 0);
     PMP_HIP_CHECK(ctx, hipMemsetAsync(queue, 0, 16, s));
     int32_t* order = nullptr;
-    if (ctx->astar_lpt && nq > workers) {
-        const int rc = lpt_order2d(ctx, s, start_xy, goal_xy, nq, W, H, &order);
+    {
+        const int rc = pmp_lpt_order(ctx, s, 2, start_xy, goal_xy, nq, ext, workers, &order);
         if (rc) return rc;
     }
     uint32_t* par = nullptr;

@@ -38,6 +38,7 @@
 // where the epoch (1..15) numbers the group's queries, so a new query needs no reset of the 1 MiB
 // array except every 15th query.  g of a CLOSED cell in a per-group f64 array (as astar2d.hip).
 #include "pmp_internal.h"
+#include "astar2d_entry.h"
 #include "grid2d.h"
 
 namespace {
@@ -50,47 +51,14 @@ constexpr int kT2Words = 1024;                  // HBM tier-2 bit blocks (levels
 constexpr int kT2LBytes = 1024;                 // LDS tier-2 bit blocks (levels 10-12, 7 bits each) per group
 constexpr int kMqLoneMax = 256;                 // batches up to this size: one query per wave (lone)
 
-// motions in the order of env.py:52-55: (-1,0),(-1,1),(0,1),(1,1),(1,0),(1,-1),(0,-1),(-1,-1)
-constexpr uint32_t kMx1 = 0x1A90u, kMy1 = 0x01A9u;
-__device__ __forceinline__ int mot_x(int d) { return (int)((kMx1 >> (2 * d)) & 3u) - 1; }
-__device__ __forceinline__ int mot_y(int d) { return (int)((kMy1 >> (2 * d)) & 3u) - 1; }
-
-// HEUR bits 0-1: 0 euclidean, 1 manhattan (GraphSearcher.h, graph_search.py:41-44), 2 zero
-// (Dijkstra); bit 2 (kThetaLayout): the Theta* entry layout of astar2d.hip -- a 5-bit code (0..7 the
-// pusher's motion, 16 + motion "path 2": the parent is the pusher's own parent, theta_star.py:104-108;
-// 8 the start) and a 13-bit dy (H <= 4096)
-constexpr int kThetaLayout = 4;
-template <int HEUR> constexpr int hkind() { return HEUR & 3; }
-template <int HEUR> constexpr int dbits() { return (HEUR & kThetaLayout) ? 5 : 4; }
-template <int HEUR>
-__device__ __forceinline__ uint32_t pack_cm(int dx, int dy, int dir)
-{
-    constexpr int S = dbits<HEUR>();
-    return ((uint32_t)dx << 18) | (((uint32_t)dy & ((1u << (18 - S)) - 1u)) << S) | (uint32_t)dir;
-}
-template <int HEUR> __device__ __forceinline__ int cm_dx(uint32_t cm) { return (int)cm >> 18; }
-template <int HEUR> __device__ __forceinline__ int cm_dy(uint32_t cm) { return (int)(cm << 14) >> (14 + dbits<HEUR>()); }
-template <int HEUR> __device__ __forceinline__ int cm_dir(uint32_t cm) { return (int)(cm & ((1u << dbits<HEUR>()) - 1u)); }
-template <int HEUR>
-__device__ __forceinline__ uint32_t hkey(uint32_t cm)
-{
-    if (hkind<HEUR>() == 2) return 0u;
-    const int dx = cm_dx<HEUR>(cm), dy = cm_dy<HEUR>(cm);
-    if (hkind<HEUR>() == 1) return (uint32_t)(abs(dx) + abs(dy));
-    return (uint32_t)(__mul24(dx, dx) + __mul24(dy, dy));
-}
+// h from its order key (the entry coding: astar2d_entry.h)
 template <int HEUR>
 __device__ __forceinline__ double h_of_key(uint32_t hk)
 {
     return hkind<HEUR>() == 2 ? 0.0 : (hkind<HEUR>() == 1 ? (double)hk : sqrt_int_rn(hk));
 }
-// Node.__lt__ (node.py:51-54)
-__device__ __forceinline__ bool key_lt(double fa, uint32_t ka, double fb, uint32_t kb)
-{
-    return (fa < fb) | ((fa == fb) & (ka < kb));
-}
-// the same as a lane mask: three compares into SGPR pairs and two scalar ops (a ballot of the bool
-// above would first turn it into a 0 / 1 VGPR and compare that again)
+// key_lt as a lane mask: three compares into SGPR pairs and two scalar ops (a ballot of key_lt's
+// bool would first turn it into a 0 / 1 VGPR and compare that again)
 __device__ __forceinline__ lmask key_lt_m(double fa, uint32_t ka, double fb, uint32_t kb)
 {
     return lm(fa < fb) | (lm(fa == fb) & lm(ka < kb));
@@ -101,9 +69,6 @@ constexpr lmask kLanesGe1 = ~0x0001000100010001ull;  // gl >= 1
 constexpr lmask kLane15 = 0x8000800080008000ull;     // gl == 15
 constexpr lmask kLanesLt8 = 0x00FF00FF00FF00FFull;   // gl < 8
 constexpr lmask kLanesLt9 = 0x01FF01FF01FF01FFull;   // gl < 9
-
-typedef __attribute__((address_space(3))) double lds_f64;
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
 
 // ---- row (16-lane group) primitives ----------------------------------------------------------
 template <int K>
@@ -138,19 +103,6 @@ __device__ __forceinline__ double bpf(double v, int src)
 }
 // my row's 16 bits of a ballot
 __device__ __forceinline__ uint32_t rbits(bool p, int gb) { return (uint32_t)(lm(p) >> gb) & 0xFFFFu; }
-
-// per lane: bit `lane` of mask ? a : b, as one v_cndmask (see astar2d.hip Ld::get)
-__device__ __forceinline__ uint32_t sel_lanes(uint64_t mask, uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_cndmask_b32_e64 %0, %2, %1, %3" : "=v"(r) : "v"(a), "v"(b), "s"(mask));
-    return r;
-}
-__device__ __forceinline__ void ds_mskor(lds_u32* w, uint32_t mask, uint32_t val)
-{
-    asm volatile("ds_mskor_b32 %0, %1, %2" ::"v"((uint32_t)(uintptr_t)w), "v"(mask), "v"(val) : "memory");
-}
-__device__ __forceinline__ void wave_sync_mem() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
 
 // ---- heap storage of one group ------------------------------------------------------------------
 struct GHeap {

@@ -22,6 +22,7 @@
 //    before the heap pop so the two overlap, with the per-slot epoch cell states of astar2d_mq.hip.
 // Control flow is uniform (one query per wave): pops and pushes take scalar branches, not selects.
 #include "pmp_internal.h"
+#include "astar2d_entry.h"
 
 namespace {
 
@@ -29,41 +30,13 @@ constexpr double kSqrt2 = 1.4142135623730951;  // math.sqrt(2) == math.hypot(1, 
 constexpr int kSqCapMax = 16383;                // heap positions 0..16382: levels 0..13
 constexpr int kSqMinCap = 1024;                 // the smallest LDS heap worth this engine
 
-// motions in the order of env.py:52-55: (-1,0),(-1,1),(0,1),(1,1),(1,0),(1,-1),(0,-1),(-1,-1)
-constexpr uint32_t kMx1 = 0x1A90u, kMy1 = 0x01A9u;
-__device__ __forceinline__ int mot_x(int d) { return (int)((kMx1 >> (2 * d)) & 3u) - 1; }
-__device__ __forceinline__ int mot_y(int d) { return (int)((kMy1 >> (2 * d)) & 3u) - 1; }
-
-// entry code: goal-relative offset and the motion that reached the cell (8 = the start)
-__device__ __forceinline__ uint32_t pack_cm(int dx, int dy, int dir)
-{
-    return ((uint32_t)dx << 18) | (((uint32_t)dy & 0x3FFFu) << 4) | (uint32_t)dir;
-}
-__device__ __forceinline__ int cm_dx(uint32_t cm) { return (int)cm >> 18; }
-__device__ __forceinline__ int cm_dy(uint32_t cm) { return (int)(cm << 14) >> 18; }
-__device__ __forceinline__ int cm_dir(uint32_t cm) { return (int)(cm & 15u); }
-// HEUR: 0 euclidean, 1 manhattan (graph_search.py:41-44), 2 zero (Dijkstra); the h order key
-template <int HEUR>
-__device__ __forceinline__ uint32_t hkey(uint32_t cm)
-{
-    if (HEUR == 2) return 0u;
-    const int dx = cm_dx(cm), dy = cm_dy(cm);
-    if (HEUR == 1) return (uint32_t)(abs(dx) + abs(dy));
-    return (uint32_t)(__mul24(dx, dx) + __mul24(dy, dy));
-}
+// HEUR: 0 euclidean, 1 manhattan (graph_search.py:41-44), 2 zero (Dijkstra): the 4-bit entry layout
+// of astar2d_entry.h; h from its order key
 template <int HEUR>
 __device__ __forceinline__ double h_of_key(uint32_t hk)
 {
     return HEUR == 2 ? 0.0 : (HEUR == 1 ? (double)hk : __dsqrt_rn((double)hk));
 }
-// Node.__lt__ (node.py:51-54): (g + h, h)
-__device__ __forceinline__ bool key_lt(double fa, uint32_t ka, double fb, uint32_t kb)
-{
-    return (fa < fb) | ((fa == fb) & (ka < kb));
-}
-
-typedef __attribute__((address_space(3))) double lds_f64;
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
 
 __device__ __forceinline__ uint64_t rl64(uint64_t v, int j)
@@ -86,7 +59,6 @@ __device__ __forceinline__ double shr1f(double v)
     const uint64_t b = (uint64_t)__double_as_longlong(v);
     return __longlong_as_double(((uint64_t)shr1((uint32_t)(b >> 32)) << 32) | shr1((uint32_t)b));
 }
-__device__ __forceinline__ void wave_sync_mem() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
 
 // LDS grid block of the LDSG variant: occupancy words, one motion byte per cell (0 = open), G
 __host__ __device__ constexpr size_t sq_occ_bytes(size_t ncell) { return (((ncell + 31) / 32) * 4 + 15) & ~(size_t)15; }
@@ -384,7 +356,7 @@ __global__ __launch_bounds__(64) void astar2d_sq_kernel(
 
     // heap[0] = Node(start, start, 0, 0), key (0, h = 0)
     double rootf = 0.0, lastf = 0.0;
-    uint32_t rootc = pack_cm(0, 0, 8), lastc = rootc;
+    uint32_t rootc = pack_cm<HEUR>(0, 0, 8), lastc = rootc;
     if (lane == 0) {
         hp.F[0] = rootf;
         hp.C[0] = rootc;
@@ -405,9 +377,9 @@ __global__ __launch_bounds__(64) void astar2d_sq_kernel(
         const uint32_t ncm = rootc;
         npop++;
         n -= 1;
-        const int ndir = cm_dir(ncm);
-        const int x = ndir == 8 ? sx : gx - cm_dx(ncm);
-        const int y = ndir == 8 ? sy : gy - cm_dy(ncm);
+        const int ndir = cm_dir<HEUR>(ncm);
+        const int x = ndir == 8 ? sx : gx - cm_dx<HEUR>(ncm);
+        const int y = ndir == 8 ? sy : gy - cm_dy<HEUR>(ncm);
         const uint32_t nlin = (uint32_t)x * (uint32_t)H + (uint32_t)y;
         // the 3x3 round, issued before the heap pop so the two overlap
         uint32_t ow, cb;
@@ -482,7 +454,7 @@ __global__ __launch_bounds__(64) void astar2d_sq_kernel(
         uint64_t vm = __ballot(nb_ok) & 0xFFull;
         const uint64_t gm = __ballot(nb_ok && ndx == 0 && ndy == 0) & 0xFFull;
         if (gm) vm &= (gm << 1) - 1ull;
-        const uint32_t icm = pack_cm(ndx, ndy, mo);
+        const uint32_t icm = pack_cm<HEUR>(ndx, ndy, mo);
         const double ifv = gnode + mcost + h_of_key<HEUR>(hkey<HEUR>(icm));
         if (n + __popcll(vm) > heap_cap) {  // a push would find n >= heap_cap
             st = PMP_CAP_OVERFLOW;

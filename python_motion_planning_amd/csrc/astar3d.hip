@@ -441,55 +441,7 @@ __global__ void a3_outside_goal_expand(const int32_t* __restrict__ s, const int3
     if (s_in && !g_in) expand[(size_t)q * expand_cap] = ((uint32_t)sx * (uint32_t)Y + (uint32_t)sy) * (uint32_t)Z + (uint32_t)sz;
 }
 
-// ---- longest-first schedule: counting sort of the queries by descending start-goal distance ----
-__device__ __forceinline__ int lpt3_key(const int32_t* s, const int32_t* g, int q)
-{
-    // in double (endpoints may lie far outside the grid: the kernels report those queries, this
-    // pre-pass must only stay in range), clamped to the histogram [0, nb - 1] by the callers
-    const double dx = (double)s[3 * q] - g[3 * q], dy = (double)s[3 * q + 1] - g[3 * q + 1],
-                 dz = (double)s[3 * q + 2] - g[3 * q + 2];
-    const double d = __dsqrt_rn(dx * dx + dy * dy + dz * dz);
-    return d < 2147483647.0 ? (int)d : 2147483647;
-}
-__global__ void lpt3_hist(const int32_t* s, const int32_t* g, int nq, int nb, int* hist)
-{
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < nq) atomicAdd(&hist[min(lpt3_key(s, g, q), nb - 1)], 1);
-}
-__global__ void lpt3_scan(int nb, int* hist)  // offsets[k] = queries with a larger key; one thread
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int run = 0;
-    for (int k = nb - 1; k >= 0; k--) {
-        const int c = hist[k];
-        hist[k] = run;
-        run += c;
-    }
-}
-__global__ void lpt3_scatter(const int32_t* s, const int32_t* g, int nq, int nb, int* offs, int32_t* order)
-{
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < nq) order[atomicAdd(&offs[min(lpt3_key(s, g, q), nb - 1)], 1)] = q;
-}
-
 }  // namespace
-
-int pmp_lpt_order3d(pmp_ctx* ctx, hipStream_t s, const int32_t* start_xyz, const int32_t* goal_xyz, int nq, int X,
-                    int Y, int Z, int workers, int32_t** order)
-{
-    *order = nullptr;
-    if (!ctx->astar_lpt || nq <= workers) return PMP_OK;
-    const int nb = (int)ceil(sqrt((double)X * X + (double)Y * Y + (double)Z * Z)) + 1;
-    int* hist = (int*)pmp_scratch(ctx, SCR_PDIR, sizeof(int) * ((size_t)nb + (size_t)nq));
-    if (!hist) return PMP_ENOMEM;
-    int32_t* ord = hist + nb;
-    PMP_HIP_CHECK(ctx, hipMemsetAsync(hist, 0, sizeof(int) * (size_t)nb, s));
-    hipLaunchKernelGGL(lpt3_hist, dim3((nq + 255) / 256), dim3(256), 0, s, start_xyz, goal_xyz, nq, nb, hist);
-    hipLaunchKernelGGL(lpt3_scan, dim3(1), dim3(64), 0, s, nb, hist);
-    hipLaunchKernelGGL(lpt3_scatter, dim3((nq + 255) / 256), dim3(256), 0, s, start_xyz, goal_xyz, nq, nb, hist, ord);
-    *order = ord;
-    return PMP_OK;
-}
 
 extern "C" int pmp_graph3d_batch(pmp_ctx* ctx, void* stream, int algo, const uint32_t* occ_bits, int per_query, int X,
                                  int Y, int Z, int heuristic, const int32_t* start_xyz, const int32_t* goal_xyz, int nq,
@@ -514,27 +466,18 @@ extern "C" int pmp_graph3d_batch(pmp_ctx* ctx, void* stream, int algo, const uin
     // workers per CU: the configured count (default 16: C5's 8192-query batches run fastest at 16-24,
     // tools/astar3d_sweep.py), but no more than the batch fills, so small batches get a larger LDS
     // heap share per worker
-    const int per_cu = std::max(1, std::min(ctx->workers_per_cu > 0 ? ctx->workers_per_cu : 16, (nq + 255) / 256));
+    const int per_cu = pmp_workers_per_cu(ctx, 16, nq);
     int workers = 256 * per_cu;
     if (workers > nq) workers = nq;
-    const size_t words = (ncell + 31) / 32;
-    bool occ_lds = words <= (size_t)kOccLdsWords;
-    // the query's bitmap in LDS takes its own size (C5: 260 words), the rest of the share is heap
-    int occ_bytes = occ_lds ? (int)((words * 4 + 15) & ~(size_t)15) : 0;
     constexpr int kEnt = heap16::lds_entry_bytes<true>(), kSpill = heap16::spill_entry_bytes<true>();
-    int lds_cap = pmp_heap_lds_cap(ctx, per_cu, occ_bytes, kEnt);
-    if (lds_cap < kMinLdsHeap && occ_lds) {  // the LDS share cannot hold the occupancy too: keep it in HBM
-        occ_lds = false;
-        occ_bytes = 0;
-        lds_cap = pmp_heap_lds_cap(ctx, per_cu, 0, kEnt);
-    }
-    if (lds_cap < kMinLdsHeap)
-        return pmp_set_err(ctx, PMP_EINVAL, "pmp_graph3d_batch: workers / resident per CU leave no LDS heap share");
     size_t hc = 26 * ncell + 8;
     if (hc > (size_t)(1 << 22)) hc = (size_t)1 << 22;
     const int heap_cap = (int)hc;
-    if (lds_cap > heap_cap) lds_cap = (heap_cap + 15) & ~15;
-    const size_t spill_n = heap_cap > lds_cap ? (size_t)(heap_cap - lds_cap) : 0;
+    // the query's bitmap in LDS takes its own size (C5: 260 words), the rest of the share is heap
+    const pmp_lds_plan lp = pmp_plan_lds(ctx, per_cu, (ncell + 31) / 32, kOccLdsWords, kEnt, heap_cap);
+    if (!lp.ok)
+        return pmp_set_err(ctx, PMP_EINVAL, "pmp_graph3d_batch: workers / resident per CU leave no LDS heap share");
+    const size_t spill_n = lp.spill_n;
     const int theta = algo == PMP_ALGO_THETA ? 1 : (algo == PMP_ALGO_LAZY_THETA ? 2 : 0);
     // theta modes: CLOSED parent per cell, and the parent of every push (indexed by the push counter;
     // a query that pushes more stops with PMP_CAP_OVERFLOW)
@@ -561,14 +504,15 @@ extern "C" int pmp_graph3d_batch(pmp_ctx* ctx, void* stream, int algo, const uin
     PMP_HIP_CHECK(ctx, hipMemsetAsync(queue, 0, 16, s));
     int32_t* order = nullptr;
     {
-        const int rc = pmp_lpt_order3d(ctx, s, start_xyz, goal_xyz, nq, X, Y, Z, workers, &order);
+        const int ext[3] = {X, Y, Z};
+        const int rc = pmp_lpt_order(ctx, s, 3, start_xyz, goal_xyz, nq, ext, workers, &order);
         if (rc) return rc;
     }
-    auto kern = occ_lds ? (theta == 1 ? astar3d_kernel<true, 1> : theta == 2 ? astar3d_kernel<true, 2> : astar3d_kernel<true, 0>)
+    auto kern = lp.occ_lds ? (theta == 1 ? astar3d_kernel<true, 1> : theta == 2 ? astar3d_kernel<true, 2> : astar3d_kernel<true, 0>)
                         : (theta == 1 ? astar3d_kernel<false, 1> : theta == 2 ? astar3d_kernel<false, 2> : astar3d_kernel<false, 0>);
-    hipLaunchKernelGGL(kern, dim3(workers), dim3(64), (size_t)lds_cap * kEnt + occ_bytes, s, occ_bits, per_query, X, Y, Z,
+    hipLaunchKernelGGL(kern, dim3(workers), dim3(64), (size_t)lp.lds_cap * kEnt + lp.occ_bytes, s, occ_bits, per_query, X, Y, Z,
                        algo == PMP_ALGO_DIJKSTRA ? 2 : heuristic, start_xyz, goal_xyz, nq, cost, path_len, path, path_cap,
-                       n_expanded, expand, expand_cap, counters, status, queue, spill, heap_cap, lds_cap, cdir, cg,
+                       n_expanded, expand, expand_cap, counters, status, queue, spill, heap_cap, lp.lds_cap, cdir, cg,
                        algo == PMP_ALGO_GBFS ? 1 : 0, theta ? tpar : nullptr, theta ? tpar + (size_t)workers * ncell : nullptr,
                        ppar_cap, (const int32_t*)order, order ? ctx->astar_prio_n : 0);
     PMP_HIP_CHECK(ctx, hipGetLastError());

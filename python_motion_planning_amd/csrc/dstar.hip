@@ -623,7 +623,7 @@ extern "C" int pmp_dstar2d_onpress_batch(pmp_ctx* ctx, void* stream, const uint3
     const size_t h1 = ctx->dstar_first_cap > 0 ? (size_t)ctx->dstar_first_cap : ncell + 64;
     const int cap1 = (int)std::min(h1, (size_t)cap_full);
     const bool two = cap1 < cap_full;
-    const int per_cu = std::max(1, std::min(ctx->workers_per_cu > 0 ? ctx->workers_per_cu : 16, (nq + 255) / 256));
+    const int per_cu = pmp_workers_per_cu(ctx, 16, nq);
     int lds_cap = (((160 * 1024) / pmp_lds_share(ctx, per_cu) - 256) / 16) & ~15;
     if (lds_cap > cap1) lds_cap = (cap1 + 15) & ~15;
     auto spill_of = [&](int cap) { return cap > lds_cap ? (size_t)(cap - lds_cap) : (size_t)0; };

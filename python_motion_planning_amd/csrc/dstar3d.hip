@@ -571,22 +571,15 @@ extern "C" int pmp_dstar3d_batch(pmp_ctx* ctx, void* stream, const uint32_t* occ
     PMP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t ncell = (size_t)X * Y * Z;
     const int words = (int)((ncell + 31) / 32);
-    bool lds_occ = words <= kOccLdsWords;
-    const int per_cu = std::max(1, std::min(ctx->workers_per_cu > 0 ? ctx->workers_per_cu : 16, (nq + 255) / 256));
-    int occ_bytes = lds_occ ? ((words * 4 + 15) & ~15) : 0;
+    const int per_cu = pmp_workers_per_cu(ctx, 16, nq);
     // heap: one valid element per OPEN voxel plus stale ones; 8 pushes per voxel bound the total
     const size_t hc = std::min<size_t>(8 * (ncell + 1) + 64, (size_t)1 << 26);
     const int heap_cap = (int)hc;
-    int lds_cap = pmp_heap_lds_cap(ctx, per_cu, occ_bytes, 16);
-    if (lds_cap < kMinLdsHeap && lds_occ) {  // the LDS share cannot hold the occupancy too: keep it in HBM
-        lds_occ = false;
-        occ_bytes = 0;
-        lds_cap = pmp_heap_lds_cap(ctx, per_cu, 0, 16);
-    }
-    if (lds_cap < kMinLdsHeap)
+    const pmp_lds_plan lp = pmp_plan_lds(ctx, per_cu, (size_t)words, kOccLdsWords, 16, heap_cap);
+    if (!lp.ok)
         return pmp_set_err(ctx, PMP_EINVAL, "pmp_dstar3d_batch: workers / resident per CU leave no LDS heap share");
-    if (lds_cap > heap_cap) lds_cap = (heap_cap + 15) & ~15;
-    const size_t spill_n = heap_cap > lds_cap ? (size_t)(heap_cap - lds_cap) : 0;
+    const bool lds_occ = lp.occ_lds;
+    const size_t spill_n = lp.spill_n;
     const size_t per_worker = (ncell + 1) * sizeof(DC3) + spill_n * 16 + (lds_occ ? 0 : (size_t)words * 4) + 256;
     int workers = 256 * per_cu;
     const size_t fit = kScratchBudget / per_worker;
@@ -602,13 +595,14 @@ extern "C" int pmp_dstar3d_batch(pmp_ctx* ctx, void* stream, const uint32_t* occ
     PMP_HIP_CHECK(ctx, hipMemsetAsync(queue, 0, 16, s));
     int32_t* order = nullptr;
     {
-        const int rc = pmp_lpt_order3d(ctx, s, start_xyz, goal_xyz, nq, X, Y, Z, workers, &order);
+        const int ext[3] = {X, Y, Z};
+        const int rc = pmp_lpt_order(ctx, s, 3, start_xyz, goal_xyz, nq, ext, workers, &order);
         if (rc) return rc;
     }
     auto kern = lds_occ ? dstar3d_kernel<true> : dstar3d_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3(workers), dim3(64), (size_t)lds_cap * 16 + occ_bytes, s, occ_bits, per_query, X, Y, Z,
+    hipLaunchKernelGGL(kern, dim3(workers), dim3(64), (size_t)lp.lds_cap * 16 + lp.occ_bytes, s, occ_bits, per_query, X, Y, Z,
                        start_xyz, goal_xyz, nq, blocks, nrounds, nblk, cost, path_len, path, path_cap, n_process, status,
-                       expand, expand_cap, max_process, queue, spill, heap_cap, lds_cap, cells, occw, words,
+                       expand, expand_cap, max_process, queue, spill, heap_cap, lp.lds_cap, cells, occw, words,
                        (const int32_t*)order, order ? ctx->astar_prio_n : 0);
     PMP_HIP_CHECK(ctx, hipGetLastError());
     return PMP_OK;

@@ -3,8 +3,9 @@
 // and the LDS word type from here; astar3d.hip and jps3d.hip also the (f, h, counter) heap key, the
 // occupancy bit of a voxel (from HBM or from the bitmap staged in LDS), the LDS occupancy threshold
 // and the per-context scratch budget (dstar3d.hip and lpa3d.hip keep their own occupancy structs,
-// threshold and budget).  The longest-first pre-pass the launchers use is pmp_lpt_order3d
-// (pmp_internal.h, defined in astar3d.hip).
+// threshold and budget).  The longest-first pre-pass the launchers use is pmp_lpt_order
+// (lpt_order.hip), their workers per CU and LDS heap plan pmp_workers_per_cu and pmp_plan_lds
+// (all three declared in pmp_internal.h).
 #pragma once
 #include "heap16.h"
 

@@ -36,14 +36,15 @@
 // first child it is less than, again one ballot.  Entries are 16 B (f, h's integer order key, push
 // number) in LDS, positions >= lds_cap in a per-worker HBM spill.
 //
-// One wave64 per query, persistent workers pulling an atomic queue, longest-first order and raised
-// priority as the A* engines.  Per-worker HBM state: g, cell and parent cell of push #seq, the
+// One wave64 per query, persistent workers pulling an atomic queue, longest-first order (lpt_order.hip)
+// and raised priority as the A* engines.  Per-worker HBM state: g, cell and parent cell of push #seq, the
 // query's CLOSED list (push numbers, in insertion order), one CLOSED bit per cell and the CLOSED push
 // number per cell (read only where the bit is set).  The bits are zero between queries: a query
 // clears them by walking its own CLOSED list.
 #include <algorithm>
 #include <cmath>
 #include "pmp_internal.h"
+#include "astar2d_entry.h"
 
 namespace {
 
@@ -53,13 +54,7 @@ constexpr int kOccLdsWords = 4096;             // both padded copies staged in L
 constexpr int kEnt = 16;                       // bytes of a heap entry
 constexpr size_t kScratchBudget = (size_t)96 << 30;  // workers are reduced to fit
 
-// motions in the order of env.py:52-55: (-1,0),(-1,1),(0,1),(1,1),(1,0),(1,-1),(0,-1),(-1,-1),
-// as 2-bit fields of (m + 1); even = axis, odd = diagonal
-constexpr uint32_t kMx1 = 0x1A90u, kMy1 = 0x01A9u;
-__device__ __forceinline__ int mot_x(int d) { return (int)((kMx1 >> (2 * d)) & 3u) - 1; }
-__device__ __forceinline__ int mot_y(int d) { return (int)((kMy1 >> (2 * d)) & 3u) - 1; }
-
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
+// motions (mot_x, mot_y: even = axis, odd = diagonal) and lds_u32 come from astar2d_entry.h
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) u32x4 lds_u4;
 
@@ -225,34 +220,6 @@ __device__ inline Ent heap_pop(const Heap& h, int n, int lane)
     if (lane == 0) hst(h, t <= lvl ? lp : pos, last);
     wsync();
     return ret;
-}
-
-// ---- longest-first schedule: counting sort by descending start-goal distance, as the A* engines
-__device__ __forceinline__ int lpt_key(const int32_t* s, const int32_t* g, int q)
-{
-    const double dx = (double)s[2 * q] - g[2 * q], dy = (double)s[2 * q + 1] - g[2 * q + 1];
-    const double d = __dsqrt_rn(dx * dx + dy * dy);
-    return d < 2147483647.0 ? (int)d : 2147483647;
-}
-__global__ void lpt_hist(const int32_t* s, const int32_t* g, int nq, int nb, int* hist)
-{
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < nq) atomicAdd(&hist[min(lpt_key(s, g, q), nb - 1)], 1);
-}
-__global__ void lpt_scan(int nb, int* hist)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int run = 0;
-    for (int k = nb - 1; k >= 0; k--) {
-        const int c = hist[k];
-        hist[k] = run;
-        run += c;
-    }
-}
-__global__ void lpt_scatter(const int32_t* s, const int32_t* g, int nq, int nb, int* offs, int32_t* order)
-{
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < nq) order[atomicAdd(&offs[min(lpt_key(s, g, q), nb - 1)], 1)] = q;
 }
 
 // ---- the search -------------------------------------------------------------------------------
@@ -505,7 +472,7 @@ extern "C" int pmp_jps2d_batch(pmp_ctx* ctx, void* stream, const uint32_t* occ_b
     // 8 per cell (a cell closes once and pushes at most 8) up to 2^20
     if (push_cap == 0) push_cap = (int)std::min<size_t>(8 * ncell + 8, (size_t)1 << 20);
     if (push_cap < 16) push_cap = 16;
-    int workers = 256 * std::max(1, std::min(ctx->workers_per_cu > 0 ? ctx->workers_per_cu : 8, (nq + 255) / 256));
+    int workers = 256 * pmp_workers_per_cu(ctx, 8, nq);
     if (workers > nq) workers = nq;
     const size_t cbit_words = (ncell + 31) / 32;
     {  // the scratch budget bounds the workers (the heap counted without its LDS part)
@@ -516,19 +483,11 @@ extern "C" int pmp_jps2d_batch(pmp_ctx* ctx, void* stream, const uint32_t* occ_b
     }
     const int per_cu = (workers + 255) / 256;  // of the workers that run: each one's LDS share
     const size_t nrows = (size_t)W * row_words(H) + (size_t)H * row_words(W);
-    bool occ_lds = nrows <= (size_t)kOccLdsWords;
-    int occ_bytes = occ_lds ? (int)((nrows * 4 + 15) & ~(size_t)15) : 0;
-    int lds_cap = pmp_heap_lds_cap(ctx, per_cu, occ_bytes, kEnt);
-    if (lds_cap < kMinLdsHeap && occ_lds) {  // the LDS share cannot hold the copies too: keep them in HBM
-        occ_lds = false;
-        occ_bytes = 0;
-        lds_cap = pmp_heap_lds_cap(ctx, per_cu, 0, kEnt);
-    }
-    if (lds_cap < kMinLdsHeap)
+    // the two padded copies are this planner's occupancy: in LDS when the share holds them beside a heap
+    const pmp_lds_plan lp = pmp_plan_lds(ctx, per_cu, nrows, kOccLdsWords, kEnt, push_cap);
+    if (!lp.ok)
         return pmp_set_err(ctx, PMP_EINVAL, "pmp_jps2d_batch: workers / resident per CU leave no LDS heap share");
-    if (lds_cap > push_cap) lds_cap = (push_cap + 15) & ~15;
-    const size_t spill_n = push_cap > lds_cap ? (size_t)(push_cap - lds_cap) : 0;
-    uint4* spill = (uint4*)pmp_scratch(ctx, SCR_AUX1, (size_t)workers * spill_n * kEnt + 16);
+    uint4* spill = (uint4*)pmp_scratch(ctx, SCR_AUX1, (size_t)workers * lp.spill_n * kEnt + 16);
     double* sg = (double*)pmp_scratch(ctx, SCR_AUX3, (size_t)workers * push_cap * 8 + 16);
     uint32_t* su = (uint32_t*)pmp_scratch(ctx, SCR_AUX4, (size_t)workers * push_cap * 12 + 16);
     uint32_t* cells = (uint32_t*)pmp_scratch(ctx, SCR_AUX2, (size_t)workers * (cbit_words + ncell) * 4 + 16);
@@ -541,20 +500,15 @@ extern "C" int pmp_jps2d_batch(pmp_ctx* ctx, void* stream, const uint32_t* occ_b
     PMP_HIP_CHECK(ctx, hipMemsetAsync(cells, 0, (size_t)workers * cbit_words * 4, s));
     hipLaunchKernelGGL(jps2d_rows, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, occ_bits, W, H, rows);
     int32_t* order = nullptr;
-    if (ctx->astar_lpt && nq > workers) {
-        const int nb = (int)ceil(sqrt((double)W * W + (double)H * H)) + 1;
-        int* hist = (int*)pmp_scratch(ctx, SCR_PDIR, sizeof(int) * ((size_t)nb + (size_t)nq));
-        if (!hist) return PMP_ENOMEM;
-        order = hist + nb;
-        PMP_HIP_CHECK(ctx, hipMemsetAsync(hist, 0, sizeof(int) * (size_t)nb, s));
-        hipLaunchKernelGGL(lpt_hist, dim3((nq + 255) / 256), dim3(256), 0, s, start_xy, goal_xy, nq, nb, hist);
-        hipLaunchKernelGGL(lpt_scan, dim3(1), dim3(64), 0, s, nb, hist);
-        hipLaunchKernelGGL(lpt_scatter, dim3((nq + 255) / 256), dim3(256), 0, s, start_xy, goal_xy, nq, nb, hist, order);
+    {
+        const int ext[2] = {W, H};
+        const int rc = pmp_lpt_order(ctx, s, 2, start_xy, goal_xy, nq, ext, workers, &order);
+        if (rc) return rc;
     }
-    auto kern = occ_lds ? jps2d_kernel<true> : jps2d_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3(workers), dim3(64), (size_t)lds_cap * kEnt + occ_bytes, s, rows, W, H, heuristic, start_xy,
+    auto kern = lp.occ_lds ? jps2d_kernel<true> : jps2d_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(workers), dim3(64), (size_t)lp.lds_cap * kEnt + lp.occ_bytes, s, rows, W, H, heuristic, start_xy,
                        goal_xy, nq, cost, path_len, path, path_cap, n_expanded, expand, expand_parent, expand_g,
-                       expand_cap, counters, status, queue, spill, push_cap, lds_cap, sg, su, cells, cbit_words,
+                       expand_cap, counters, status, queue, spill, push_cap, lp.lds_cap, sg, su, cells, cbit_words,
                        (const int32_t*)order, order ? ctx->astar_prio_n : 0);
     PMP_HIP_CHECK(ctx, hipGetLastError());
     return PMP_OK;

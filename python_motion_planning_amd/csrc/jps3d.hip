@@ -380,26 +380,17 @@ extern "C" int pmp_jps3d_batch(pmp_ctx* ctx, void* stream, const uint32_t* occ_b
     PMP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t ncell = (size_t)X * Y * Z;
     // workers, LDS heap share and scratch budget as pmp_graph3d_batch (astar3d.hip)
-    const int per_cu = std::max(1, std::min(ctx->workers_per_cu > 0 ? ctx->workers_per_cu : 16, (nq + 255) / 256));
+    const int per_cu = pmp_workers_per_cu(ctx, 16, nq);
     int workers = 256 * per_cu;
     if (workers > nq) workers = nq;
-    const size_t words = (ncell + 31) / 32;
-    bool occ_lds = words <= (size_t)kOccLdsWords;
-    int occ_bytes = occ_lds ? (int)((words * 4 + 15) & ~(size_t)15) : 0;
     constexpr int kEnt = heap16::lds_entry_bytes<true>(), kSpill = heap16::spill_entry_bytes<true>();
-    int lds_cap = pmp_heap_lds_cap(ctx, per_cu, occ_bytes, kEnt);
-    if (lds_cap < kMinLdsHeap && occ_lds) {  // the LDS share cannot hold the occupancy too: keep it in HBM
-        occ_lds = false;
-        occ_bytes = 0;
-        lds_cap = pmp_heap_lds_cap(ctx, per_cu, 0, kEnt);
-    }
-    if (lds_cap < kMinLdsHeap)
-        return pmp_set_err(ctx, PMP_EINVAL, "pmp_jps3d_batch: workers / resident per CU leave no LDS heap share");
     size_t hc = 26 * ncell + 8;
     if (hc > (size_t)(1 << 22)) hc = (size_t)1 << 22;
     const int heap_cap = (int)hc;
-    if (lds_cap > heap_cap) lds_cap = (heap_cap + 15) & ~15;
-    const size_t spill_n = heap_cap > lds_cap ? (size_t)(heap_cap - lds_cap) : 0;
+    const pmp_lds_plan lp = pmp_plan_lds(ctx, per_cu, (ncell + 31) / 32, kOccLdsWords, kEnt, heap_cap);
+    if (!lp.ok)
+        return pmp_set_err(ctx, PMP_EINVAL, "pmp_jps3d_batch: workers / resident per CU leave no LDS heap share");
+    const size_t spill_n = lp.spill_n;
     // the parent of every push, indexed by the push counter (a query that pushes more stops with PMP_CAP_OVERFLOW)
     const uint32_t ppar_cap = (uint32_t)std::min<size_t>(64 * ncell + 64, (size_t)1 << 24);
     {
@@ -417,13 +408,14 @@ extern "C" int pmp_jps3d_batch(pmp_ctx* ctx, void* stream, const uint32_t* occ_b
     PMP_HIP_CHECK(ctx, hipMemsetAsync(queue, 0, 16, s));
     int32_t* order = nullptr;
     {
-        const int rc = pmp_lpt_order3d(ctx, s, start_xyz, goal_xyz, nq, X, Y, Z, workers, &order);
+        const int ext[3] = {X, Y, Z};
+        const int rc = pmp_lpt_order(ctx, s, 3, start_xyz, goal_xyz, nq, ext, workers, &order);
         if (rc) return rc;
     }
-    auto kern = occ_lds ? jps3d_kernel<true> : jps3d_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3(workers), dim3(64), (size_t)lds_cap * kEnt + occ_bytes, s, occ_bits, per_query, X, Y, Z,
+    auto kern = lp.occ_lds ? jps3d_kernel<true> : jps3d_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(workers), dim3(64), (size_t)lp.lds_cap * kEnt + lp.occ_bytes, s, occ_bits, per_query, X, Y, Z,
                        heuristic, start_xyz, goal_xyz, nq, cost, path_len, path, path_cap, n_expanded, expand, expand_parent,
-                       expand_g, expand_cap, counters, status, queue, spill, heap_cap, lds_cap, cg, tpar,
+                       expand_g, expand_cap, counters, status, queue, spill, heap_cap, lp.lds_cap, cg, tpar,
                        tpar + (size_t)workers * ncell, ppar_cap, (const int32_t*)order, order ? ctx->astar_prio_n : 0);
     PMP_HIP_CHECK(ctx, hipGetLastError());
     return PMP_OK;

@@ -867,7 +867,7 @@ extern "C" int pmp_lpastar3d_batch(pmp_ctx* ctx, void* stream, const uint32_t* o
     const bool occ_lds = words <= kOccLdsWords;
     // up to 16 waves per CU (tools/dyn3d_sweep.py): the LDS share of each holds the g block, U (20 B per
     // entry, the rest spills) and the occupancy
-    const int per_cu = std::max(1, std::min(ctx->workers_per_cu > 0 ? ctx->workers_per_cu : 16, (nq + 255) / 256));
+    const int per_cu = pmp_workers_per_cu(ctx, 16, nq);
     const int occ_bytes = occ_lds ? ((words * 4 + 15) & ~15) : 0;
     int ucap = (((160 * 1024) / per_cu - 1024 - occ_bytes) / 20) & ~15;
     if (ucap < 64) ucap = 64;
@@ -890,7 +890,8 @@ extern "C" int pmp_lpastar3d_batch(pmp_ctx* ctx, void* stream, const uint32_t* o
     PMP_HIP_CHECK(ctx, hipMemsetAsync(queue, 0, 16, s));
     int32_t* order = nullptr;
     {
-        const int rc = pmp_lpt_order3d(ctx, s, start_xyz, goal_xyz, nq, X, Y, Z, workers, &order);
+        const int ext[3] = {X, Y, Z};
+        const int rc = pmp_lpt_order(ctx, s, 3, start_xyz, goal_xyz, nq, ext, workers, &order);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(lpa3d_kernel, dim3(workers), dim3(64), lds, s, occ_bits, per_query, X, Y, Z, heuristic, start_xyz,

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <string>
 
 #include "../../include/pmp.h"
@@ -72,11 +73,48 @@ inline int pmp_heap_lds_cap(const pmp_ctx* ctx, int per_cu, int fixed_bytes, int
 // Ensure scratch buffer `slot` holds at least `bytes`; returns device pointer or nullptr (error set).
 void* pmp_scratch(pmp_ctx* ctx, int slot, size_t bytes);
 
-// Longest-first order of a 3D batch (descending start-goal distance, counting sort on `s`) in the
+// Workers per CU of a one-wave-per-query launch: the configured count (pmp_set_workers_per_cu, else the
+// planner's default `dflt`), but no more than the batch fills, so small batches get a larger LDS heap
+// share per worker.
+inline int pmp_workers_per_cu(const pmp_ctx* ctx, int dflt, int nq)
+{
+    return std::max(1, std::min(ctx->workers_per_cu > 0 ? ctx->workers_per_cu : dflt, (nq + 255) / 256));
+}
+// How a one-wave-per-query launch of `per_cu` workers per CU splits a worker's LDS share between the
+// query's occupancy words and its heap (`entry_bytes` per position, `heap_cap` positions in all).  The
+// occupancy goes to LDS when it has at most `occ_lds_words` words (the caller's threshold) and the
+// share still holds a heap beside it; otherwise it stays in HBM and the whole share is heap.  ok =
+// false: even then the share holds no heap, and the caller refuses the launch.  lds_cap is clamped to
+// the heap capacity; spill_n = the positions beyond it, kept in HBM.
+struct pmp_lds_plan {
+    bool ok, occ_lds;
+    int occ_bytes, lds_cap;
+    size_t spill_n;
+};
+inline pmp_lds_plan pmp_plan_lds(const pmp_ctx* ctx, int per_cu, size_t occ_words, size_t occ_lds_words, int entry_bytes,
+                                 int heap_cap)
+{
+    pmp_lds_plan p;
+    p.occ_lds = occ_words <= occ_lds_words;
+    p.occ_bytes = p.occ_lds ? (int)((occ_words * 4 + 15) & ~(size_t)15) : 0;
+    p.lds_cap = pmp_heap_lds_cap(ctx, per_cu, p.occ_bytes, entry_bytes);
+    if (p.lds_cap < kMinLdsHeap && p.occ_lds) {  // the LDS share cannot hold the occupancy too: keep it in HBM
+        p.occ_lds = false;
+        p.occ_bytes = 0;
+        p.lds_cap = pmp_heap_lds_cap(ctx, per_cu, 0, entry_bytes);
+    }
+    p.ok = p.lds_cap >= kMinLdsHeap;
+    if (p.lds_cap > heap_cap) p.lds_cap = (heap_cap + 15) & ~15;
+    p.spill_n = heap_cap > p.lds_cap ? (size_t)(heap_cap - p.lds_cap) : 0;
+    return p;
+}
+
+// Longest-first order of a batch of `dims`-coordinate (2 or 3) queries on a grid of `extent` (W, H or
+// X, Y, Z): descending start-goal distance, a counting sort on `s` with ceil(diagonal) + 1 bins, in the
 // context's SCR_PDIR scratch; *order = nullptr when the schedule is off or every query has its own
-// worker (nq <= workers).  Shared by the one-wave-per-query 3D planners (astar3d.hip).
-int pmp_lpt_order3d(pmp_ctx* ctx, hipStream_t s, const int32_t* start_xyz, const int32_t* goal_xyz, int nq, int X,
-                    int Y, int Z, int workers, int32_t** order);
+// worker (nq <= workers).  Shared by every persistent-worker grid planner (lpt_order.hip).
+int pmp_lpt_order(pmp_ctx* ctx, hipStream_t s, int dims, const int32_t* start, const int32_t* goal, int nq,
+                  const int* extent, int workers, int32_t** order);
 
 // The multi-query A* 2D engine (astar2d_mq.hip), driven by pmp_graph2d_batch (astar2d.hip).
 int pmp_astar2d_mq_launch(pmp_ctx* ctx, hipStream_t s, int algo, const uint32_t* occ_bits, int W, int H, int heuristic,

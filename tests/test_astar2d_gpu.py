@@ -371,6 +371,60 @@ def test_residency_batches_in_flight(eng, per_cu):
         L.pmp_destroy(b["ctx"])
 
 
+@pytest.mark.parametrize("eng", [0, 2], ids=["wave", "mq"])
+def test_longest_first_order_clamps_far_endpoints(eng):
+    """The longest-first pre-pass (lpt_order.hip) on endpoints far outside the grid.  The README grid
+    (51 x 31) has ceil(diagonal) + 1 = 61 bins; 12 queries on 4 reserved workers (nq > workers, so the
+    order is built), two of them with an endpoint hundreds of cells away: their keys (700 and 445)
+    lie beyond the last bin and must be clamped to it, not index past the histogram.  Those two report
+    status 1 like any endpoint outside the grid (test_edge_cases); the other ten equal the oracle, and
+    the records are the same with the schedule off (input order) and on."""
+    import torch
+
+    from oracle import oracle as O
+    from python_motion_planning_amd import _lib, batch, workloads as wl
+
+    occ = wl.readme_grid()
+    W, H = occ.shape
+    assert (W, H) == (51, 31)
+    free = np.argwhere(occ == 0)
+    rng = np.random.default_rng(20)
+    s = np.vstack([free[rng.integers(len(free), size=10)], [[5, 5]], [[-400, 3]]]).astype(np.int32)
+    g = np.vstack([free[rng.integers(len(free), size=10)], [[500, 500]], [[45, 25]]]).astype(np.int32)
+    nq, pc = len(s), W * H + 1
+    ref = O.astar2d_batch(occ, s[:10], g[:10], path_cap=pc)
+    L = _lib.load_library()
+    bits = batch.occ_bits_device(occ, torch)
+    s_d, g_d = torch.as_tensor(s, device="cuda"), torch.as_tensor(g, device="cuda")
+    ctx = L.pmp_create(torch.cuda.current_device())
+    records = []
+    try:
+        _lib.check(ctx, L.pmp_astar2d_set_engine(ctx, eng, 0), "engine")
+        _lib.check(ctx, L.pmp_astar2d_reserve(ctx, W, H, 4, 0), "reserve")
+        for longest_first in (0, 1):
+            _lib.check(ctx, L.pmp_astar2d_set_schedule(ctx, longest_first), "schedule")
+            c = torch.full((nq,), -1.0, dtype=torch.float64, device="cuda")
+            pl, ne, st = (torch.full((nq,), -1, dtype=torch.int32, device="cuda") for _ in range(3))
+            p = torch.zeros((nq, pc), dtype=torch.int32, device="cuda")
+            rc = L.pmp_astar2d_batch(ctx, None, bits.data_ptr(), W, H, 0, s_d.data_ptr(), g_d.data_ptr(), nq,
+                                     c.data_ptr(), pl.data_ptr(), p.data_ptr(), pc, ne.data_ptr(), None, 0, None,
+                                     st.data_ptr())
+            _lib.check(ctx, rc, "pmp_astar2d_batch")
+            torch.cuda.synchronize()
+            records.append(tuple(t.cpu().numpy() for t in (st, c, pl, ne, p)))
+    finally:
+        L.pmp_destroy(ctx)
+    for st, c, pl, ne, p in records:
+        assert st[10:].tolist() == [1, 1]
+        assert (st[:10] == ref["status"]).all()
+        assert (c[:10].view(np.int64) == ref["cost"].view(np.int64)).all()
+        assert (ne[:10] == ref["n_expanded"]).all() and (pl[:10] == ref["path_len"]).all()
+        for q in range(10):
+            assert (p[q, : pl[q]] == ref["path"][q, : pl[q]]).all()
+    for off, on in zip(*records):  # every output array, bit for bit (the path rows start zeroed)
+        assert off.tobytes() == on.tobytes()
+
+
 @pytest.mark.parametrize("per_cu", [56, 60], ids=["56_per_cu", "60_per_cu"])
 def test_c2_headline_schedule_against_oracle(per_cu):
     """The bench's headline schedule (engine 2, 14,336 groups = 56 per CU since round 6, and round 5's

@@ -24,8 +24,11 @@ import sqlite3
 import sys
 
 KERNELS = {  # short name -> regex on the demangled kernel name
-    "lpt_hist": r"lpt_hist\(", "lpt_scan": r"lpt_scan\(", "lpt_scatter": r"lpt_scatter\(",
-    "lpt3_hist": r"lpt3_hist\(", "lpt3_scan": r"lpt3_scan\(", "lpt3_scatter": r"lpt3_scatter\(",
+    # the longest-first pre-pass (lpt_order.hip: lpt_hist<2 or 3>, lpt_scan, lpt_scatter<2 or 3>); the
+    # lpt3_* names are the 3D copies in databases recorded before the pre-pass was shared
+    "lpt_hist": r"lpt_hist(<2>)?\(", "lpt_scan": r"lpt_scan\(", "lpt_scatter": r"lpt_scatter(<2>)?\(",
+    "lpt3_hist": r"lpt3_hist\(|lpt_hist<3>\(", "lpt3_scan": r"lpt3_scan\(",
+    "lpt3_scatter": r"lpt3_scatter\(|lpt_scatter<3>\(",
     "dwa_kernel": r"\bdwa_kernel[<(]",
     "dwa_split_kernel": r"\bdwa_split_kernel[<(]",
     "rrt_kernel": r"\brrt_kernel[<(]",
