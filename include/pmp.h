@@ -632,6 +632,54 @@ int pmp_totp3d_batch(pmp_ctx* ctx, void* stream, const pmp_totp_params* prm, int
                      double* s_ddot, double* time_profile, int32_t* n_samples, int point_cap, double* points,
                      int32_t* n_points, double* total_time, int32_t* status, const double* eval_t, int n_eval);
 
+/* TrajectoryConstraints (trajectory/trajectory_base.py:30-45) as PolynomialTrajectory3D reads them */
+typedef struct {
+    double max_velocity[3];
+    double max_acceleration[3];
+    double min_time_step;
+} pmp_polytraj_params;
+
+/*
+ * Batched quintic trajectories (the `polynomial` choice after 3D planning, examples/3d_example.py:100-133).
+ * Replaces PolynomialTrajectory3D(path, constraints, boundary_conditions).generate() / evaluate(t) /
+ * resample(dt) (trajectory/polynomial_trajectory.py:52-286, trajectory_base.py:193-216): segment times
+ * T_i = max(d_i / (min(vmax) 0.7), 2 sqrt(d_i / min(amax)), 0.5) (:89-111), their left-to-right running
+ * sum (segment starts and total_time), centred-difference waypoint velocities clipped to +-vmax
+ * (:162-187), zero interior accelerations, quintic coefficients per axis and segment (:142-158,
+ * recomputed per point, never stored), sampling at t = 0, dt, ... by repeated addition (+ total_time when
+ * the last step is short of it, :238-246), evaluate(t) (:253-286: t clipped to [0, total_time], the first
+ * segment with t <= start + duration), yaw / yaw rate (trajectory_base.py:245-261).  Times, counts and
+ * segment_times of integer waypoints are bit-equal to the reference's; rows match it to rounding.
+ *   paths, one of two forms (the other's pointers NULL):
+ *     path_xyz [sum n][3] f64, path_off [nq + 1] i32   waypoints per path (reference order)
+ *     cells [nq][path_cap] i32, path_len [nq] i32, X, Y, Z   cell ids (x Y Z + y Z + z) as
+ *       pmp_graph3d_batch leaves them on the device, decoded in the order given
+ *   bc [nq][4][3] f64 nullable: initial velocity, final velocity, initial acceleration, final
+ *       acceleration per path; NULL = zeros
+ *   max_waypoints  >= every path's n (sizes LDS; 2 .. pmp_polytraj3d_max_waypoints() = 880)
+ *   points [nq][point_cap][15]: time, position[3], velocity[3], acceleration[3], jerk[3], yaw, yaw rate
+ *       (NaN where the reference leaves None); n_points [nq]; total_time [nq]
+ *   segment_times: path q's n - 1 durations start at path_off[q] (buffer of sum n doubles), in the
+ *       cells form at q * path_cap (buffer [nq][path_cap])
+ *   status [nq]  0 ok, 2 point_cap too small (the count is still reported; a path of more than 2^24
+ *                steps reports count 0), 3 more waypoints than max_waypoints (or path_cap), 4 the
+ *                reference raises (< 2 waypoints) or never ends (total_time not finite)
+ *   eval_t [n_eval] nullable: instead of generate()'s sampling, evaluate(t) at these times (yaw / yaw
+ *       rate NaN, as evaluate leaves them)
+ *   sample_dt  > 0: resample(sample_dt): the same repeated sum with this step, yaw / yaw rate NaN;
+ *       0: generate() with min_time_step
+ * Refused with PMP_EINVAL (the reference divides by zero or never leaves its sampling loop):
+ * min(max_acceleration) <= 0, non-finite constraints, min_time_step <= 0.  Repeated consecutive
+ * waypoints are legal (T = 0.5).
+ */
+int pmp_polytraj3d_batch(pmp_ctx* ctx, void* stream, const pmp_polytraj_params* prm, int nq, const double* path_xyz,
+                         const int32_t* path_off, const int32_t* cells, const int32_t* path_len, int path_cap, int X,
+                         int Y, int Z, const double* bc, int max_waypoints, int point_cap, double* points,
+                         int32_t* n_points, double* total_time, double* segment_times, int32_t* status,
+                         const double* eval_t, int n_eval, double sample_dt);
+/* The largest max_waypoints pmp_polytraj3d_batch accepts (its LDS block beside the row stage). */
+int pmp_polytraj3d_max_waypoints(void);
+
 /* Launch-span recording for profiling: while set, every A* 2D launch of this context folds its
  * workers' first start and last end wall-clock ticks into span[0] (atomic min) and span[1] (atomic
  * max); the caller initialises span to {UINT64_MAX, 0}.  NULL switches it off. */

@@ -79,6 +79,9 @@ SIGNATURES = {
                                    _vp, _vp, _vp, _vp]),
     "pmp_totp3d_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
                               _vp, _i]),
+    "pmp_polytraj3d_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _i, ctypes.c_double]),
+    "pmp_polytraj3d_max_waypoints": (_i, []),
 }
 
 
@@ -157,6 +160,18 @@ class TotpParams(ctypes.Structure):
         return cls((ctypes.c_double * 3)(*[float(v) for v in max_velocity]),
                    (ctypes.c_double * 3)(*[float(v) for v in max_acceleration]), float(min_time_step),
                    float(path_resolution))
+
+
+class PolyTrajParams(ctypes.Structure):
+    """pmp_polytraj_params == TrajectoryConstraints (trajectory/trajectory_base.py:30-45) max_velocity,
+    max_acceleration, min_time_step as PolynomialTrajectory3D reads them."""
+    _fields_ = [("max_velocity", ctypes.c_double * 3), ("max_acceleration", ctypes.c_double * 3),
+                ("min_time_step", ctypes.c_double)]
+
+    @classmethod
+    def make(cls, max_velocity=(2.0, 2.0, 2.0), max_acceleration=(1.0, 1.0, 1.0), min_time_step: float = 0.01):
+        return cls((ctypes.c_double * 3)(*[float(v) for v in max_velocity]),
+                   (ctypes.c_double * 3)(*[float(v) for v in max_acceleration]), float(min_time_step))
 
 
 TRACK_LQR, TRACK_MPC = 0, 1

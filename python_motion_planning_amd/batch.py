@@ -951,3 +951,112 @@ def totp3d_batch(paths, params, point_cap: int | None = None, eval_t=None, retry
             for k in ("s_values", "s_dot", "s_ddot", "time", "n_samples", "n_points", "total_time", "status"):
                 out[k][idx] = r[k]
     return out
+
+
+def polytraj_segment_times(path, params):
+    """numpy restatement of _compute_segment_times (trajectory/polynomial_trajectory.py:89-111) for one
+    [n, 3] path: sizes point_cap (the kernel computes its own)."""
+    d = np.sqrt(np.sum(np.diff(np.asarray(path, np.float64).reshape(-1, 3), axis=0) ** 2, axis=1))
+    vavg = min(params.max_velocity) * 0.7
+    est = d / vavg if vavg > 0 else np.ones_like(d)
+    return np.maximum(np.maximum(est, 2.0 * np.sqrt(d / min(params.max_acceleration))), 0.5)
+
+
+def polytraj3d_batch(paths, params, bc=None, point_cap: int | None = None, eval_t=None, sample_dt: float | None = None,
+                     retry_overflow: bool = True, cells=None, max_waypoints: int | None = None):
+    """Batched PolynomialTrajectory3D(path, constraints, boundary_conditions).generate()
+    (trajectory/polynomial_trajectory.py:189-251) on pmp_polytraj3d_batch.  paths: list of [n, 3]
+    waypoint arrays (reference order), or None with cells=(path, path_len, (X, Y, Z)): the device
+    tensors a 3D grid planner returned (batch.astar3d_batch's "path", "path_len" and grid size), decoded
+    on the device.  params: _lib.PolyTrajParams.  bc [nq, 4, 3]: initial / final velocity, initial / final
+    acceleration per path (None = zeros).  With eval_t (1-D times), evaluate(t) (:253-286) at those times
+    instead of generate()'s sampling; with sample_dt, resample(sample_dt) (trajectory_base.py:193-216).
+    Returns dict of device tensors: points [nq, point_cap, 15] (time, position, velocity, acceleration,
+    jerk, yaw, yaw rate; NaN = None), n_points, total_time, status, segment_times (flat, path q's n - 1
+    values from seg_off[q]; [nq, path_cap] in the cells form) (include/pmp.h).  Paths whose points
+    overflow the first cap are re-run with their exact count when retry_overflow."""
+    torch = _lib.device_check()
+    L = _lib.load_library()
+    ctx = _lib.context()
+    wp_limit = int(L.pmp_polytraj3d_max_waypoints())
+    dt = float(params.min_time_step) if sample_dt is None else float(sample_dt)
+    if sample_dt is not None and not dt > 0:
+        raise ValueError("sample_dt must be > 0")
+    et = None if eval_t is None else torch.as_tensor(np.asarray(eval_t, np.float64).ravel(), device="cuda")
+    n_eval = 0 if et is None else int(et.numel())
+    tmax = None  # an upper bound of the batch's total_time
+    if cells is None:
+        arrs = [np.asarray(p, np.float64).reshape(-1, 3) for p in paths]
+        nq = len(arrs)
+        off = np.zeros(nq + 1, np.int32)
+        off[1:] = np.cumsum([len(a) for a in arrs])
+        nmax = max((len(a) for a in arrs), default=2)
+        src = (torch.as_tensor(np.concatenate(arrs) if nq else np.zeros((0, 3)), device="cuda"),
+               torch.as_tensor(off, device="cuda"))
+        path_cap, dims = 0, (0, 0, 0)
+        if np.isfinite(dt) and dt > 0 and min(params.max_acceleration) > 0:
+            with np.errstate(all="ignore"):
+                tmax = max((float(np.sum(polytraj_segment_times(a, params))) for a in arrs if len(a) > 1), default=0.0)
+    else:
+        cp, cl, dims = cells
+        cp = _dev(torch, cp, torch.int32)
+        cl = _dev(torch, cl, torch.int32).reshape(-1)
+        nq, path_cap = int(cp.shape[0]), int(cp.shape[1])
+        src = (cp, cl)
+        dims = tuple(int(v) for v in dims)
+        nmax = int(cl.max().item()) if max_waypoints is None and nq else 2
+        if np.isfinite(dt) and dt > 0 and min(params.max_acceleration) > 0:
+            # neighbouring cells are at most sqrt(3) apart (any-angle paths may overflow: retried)
+            tmax = (max(nmax, int(max_waypoints or 0)) - 1) * float(polytraj_segment_times([[0, 0, 0], [1, 1, 1]], params)[0])
+    nmax = int(max_waypoints) if max_waypoints is not None else min(max(2, nmax), wp_limit)
+    if point_cap is None:
+        if et is not None:
+            point_cap = n_eval + 1
+        else:
+            point_cap = int(min(tmax / dt, float(1 << 24))) + 3 if tmax is not None and np.isfinite(tmax) else 2048
+    bcd = None if bc is None else _dev(torch, bc, torch.float64).reshape(nq, 4, 3)
+
+    def launch(a, b, bcs, pc):
+        m = int(b.shape[0]) - 1 if cells is None else int(b.shape[0])
+        f64 = dict(dtype=torch.float64, device="cuda")
+        i32 = dict(dtype=torch.int32, device="cuda")
+        o = dict(points=torch.empty((m, pc, 15), **f64), n_points=torch.empty(m, **i32), total_time=torch.empty(m, **f64),
+                 status=torch.empty(m, **i32),
+                 segment_times=torch.zeros(int(a.shape[0]) if cells is None else (m, path_cap), **f64))
+        if cells is None:
+            args = (a.data_ptr(), b.data_ptr(), None, None, 0, 0, 0, 0)
+        else:
+            args = (None, None, a.data_ptr(), b.data_ptr(), path_cap) + dims
+        rc = L.pmp_polytraj3d_batch(ctx, _lib.stream_ptr(), ctypes.byref(params), m, *args, _lib.ptr(bcs), nmax, pc,
+                                    o["points"].data_ptr(), o["n_points"].data_ptr(), o["total_time"].data_ptr(),
+                                    o["segment_times"].data_ptr(), o["status"].data_ptr(), _lib.ptr(et), n_eval,
+                                    0.0 if sample_dt is None else dt)
+        _lib.check(ctx, rc, "pmp_polytraj3d_batch")
+        return o
+
+    out = launch(src[0], src[1], bcd, int(point_cap))
+    if cells is None:
+        out["seg_off"] = off
+    if retry_overflow and nq:
+        st = out["status"].cpu().numpy()
+        npt = out["n_points"].cpu().numpy()
+        redo = np.nonzero((st == _lib.STATUS_PATH_OVERFLOW) & (npt > point_cap))[0]
+        if len(redo):
+            pc = int(npt[redo].max())
+            idx = torch.as_tensor(redo, device="cuda", dtype=torch.long)
+            if cells is None:
+                sub = [arrs[i] for i in redo]
+                so = np.zeros(len(sub) + 1, np.int32)
+                so[1:] = np.cumsum([len(a) for a in sub])
+                r = launch(torch.as_tensor(np.concatenate(sub), device="cuda"), torch.as_tensor(so, device="cuda"),
+                           None if bcd is None else bcd[idx].contiguous(), pc)
+            else:
+                r = launch(src[0][idx].contiguous(), src[1][idx].contiguous(),
+                           None if bcd is None else bcd[idx].contiguous(), pc)
+            big = torch.full((nq, pc, 15), float("nan"), dtype=torch.float64, device="cuda")
+            big[:, : int(point_cap)] = out["points"]
+            big[idx] = r["points"]
+            out["points"] = big
+            for k in ("n_points", "total_time", "status"):
+                out[k][idx] = r[k]
+    return out

@@ -15,6 +15,7 @@
 // Values follow the reference's operation order (CPython / numpy float64, -ffp-contract=off), so
 // results match it to rounding (the parity tests bound them at 1e-9 relative).
 #include "pmp_internal.h"
+#include "traj_sample.h"
 
 namespace {
 
@@ -433,40 +434,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void to
     double t = 0.0, last_t = -1.0;  // lane 0: the reference's accumulated t
     int count = 0;
     bool done = false;
-    double prev_t = 0.0, prev_yaw = 0.0;  // the previous point (wave-uniform)
-    bool prev_has = false, prev_yaw_ok = false;
+    traj_prev pv;  // the previous point (wave-uniform)
     while (!done) {
-        if (lane == 0) {
-            int k = 0;
-            bool fin = false;
-            if (eval_t) {
-                for (; k < kCh && count + k < n_eval; k++) tq[k] = eval_t[count + k];
-                fin = count + k >= n_eval;
-            } else {
-                while (k < kCh) {
-                    if (t <= total) {
-                        tq[k++] = t;
-                        last_t = t;
-                        t += T.min_time_step;
-                    } else {
-                        if (count + k > 0 && last_t < total) {
-                            tq[k++] = total;
-                            last_t = total;
-                        }
-                        fin = true;
-                        break;
-                    }
-                }
-            }
-            meta[0] = k;
-            meta[1] = fin ? 1 : 0;
-        }
+        if (lane == 0) traj_next_times(eval_t, n_eval, count, T.min_time_step, total, t, last_t, tq, meta);
         __syncthreads();
         const int k = meta[0];
         done = meta[1] != 0;
-        double my_t = 0.0, yaw = 0.0;
-        bool has = false;
+        double my_t = 0.0;
         double o[12];
+        o[4] = 0.0;
+        o[5] = 0.0;
         if (lane < k) {
             const double tc = tq[lane] < 0.0 ? 0.0 : (tq[lane] > total ? total : tq[lane]);
             // interp1d(kind='linear', fill_value='extrapolate') (scipy _call_linear): searchsorted
@@ -493,35 +470,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void to
                 o[7 + d] = q2[d] * (sdt * sdt) + q1[d] * sddt;
             }
             my_t = tc;
-            has = !eval_t && __dsqrt_rn(o[4] * o[4] + o[5] * o[5]) > 1e-6;
-            yaw = has ? atan2(o[5], o[4]) : 0.0;
-            o[10] = has ? yaw : __longlong_as_double(0x7ff8000000000000ll);
         }
-        // yaw rate from the previous point: lane - 1, or the previous round's last point (all lanes
-        // take part in the shuffles)
-        const double pt = __shfl_up(my_t, 1), py = __shfl_up(yaw, 1);
-        const bool ph = __shfl_up(has ? 1 : 0, 1) != 0;
+        // yaw, and the yaw rate from the previous point (traj_sample.h)
+        traj_yaw_tail(lane, k, !eval_t, o[4], o[5], my_t, pv, o[10], o[11]);
         if (lane < k) {
-            const double qt = lane == 0 ? prev_t : pt, qy = lane == 0 ? prev_yaw : py;
-            const bool qh = lane == 0 ? (prev_has && prev_yaw_ok) : ph;
-            double rate = __longlong_as_double(0x7ff8000000000000ll);
-            const double dtp = my_t - qt;
-            if (qh && has && dtp > 0) {
-                double dy = yaw - qy;
-                while (dy > M_PI) dy -= 2.0 * M_PI;
-                while (dy < -M_PI) dy += 2.0 * M_PI;
-                rate = dy / dtp;
-            }
-            o[11] = rate;
             const int idx = count + lane;
             if (idx < point_cap)
                 for (int j = 0; j < 12; j++) pts[(size_t)idx * 12 + j] = o[j];
-        }
-        if (k > 0) {
-            prev_t = rl_f64(my_t, k - 1);
-            prev_yaw = rl_f64(yaw, k - 1);
-            prev_yaw_ok = rl_u32(has ? 1u : 0u, k - 1) != 0;
-            prev_has = true;
         }
         count += k;
         __syncthreads();

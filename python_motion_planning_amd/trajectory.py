@@ -5,6 +5,9 @@ on the gfx950 kernel pmp_totp3d_batch: the config-5 step after 3D planning
 Same constructor, attributes and return values as the reference (TrajectoryPoint /
 TrajectoryConstraints dataclasses as in trajectory/trajectory_base.py:8-45); generate() and
 evaluate() run on the GPU.  For many paths at once use batch.totp3d_batch.
+
+Drop-in PolynomialTrajectory3D (trajectory/polynomial_trajectory.py:52-331, the example's `polynomial`
+choice, examples/3d_example.py:112-117) on pmp_polytraj3d_batch, batched by batch.polytraj3d_batch.
 """
 from __future__ import annotations
 
@@ -149,4 +152,142 @@ class TimeOptimalTrajectory3D:
             res["velocity_satisfied"] = False
         if np.any(np.max(np.abs(self.get_accelerations()), axis=0) > self.constraints.max_acceleration):
             res["acceleration_satisfied"] = False
+        return res
+
+
+_BC_KEYS = ("initial_velocity", "final_velocity", "initial_acceleration", "final_acceleration")
+
+
+class PolynomialTrajectory3D:
+    """polynomial_trajectory.py:52-331 (quintic segments through the waypoints) on pmp_polytraj3d_batch:
+    generate(), evaluate() and resample() run on the GPU; optimize_time_allocation() is the reference's
+    host loop around generate().  For many paths at once use batch.polytraj3d_batch."""
+
+    def __init__(self, path, constraints: Optional[TrajectoryConstraints] = None,
+                 boundary_conditions: Optional[dict] = None):
+        if not path:
+            raise ValueError("Path cannot be empty")
+        # _process_path (trajectory_base.py:79-95): 2D points get z = 0
+        self.dimension = 3
+        self.path = np.array([[p[0], p[1], 0.0] if len(p) == 2 else list(p) for p in path], dtype=float)
+        if constraints is None:
+            constraints = TrajectoryConstraints(np.array([2.0] * 3), np.array([1.0] * 3))
+        self.constraints = constraints
+        self.trajectory_points: List[TrajectoryPoint] = []
+        self.total_time = 0.0
+        self.segment_times: List[float] = []
+        self.boundary_conditions = boundary_conditions or {}
+        for k in _BC_KEYS:
+            if k not in self.boundary_conditions:
+                self.boundary_conditions[k] = np.zeros(3)
+        self._generated_total = None  # total_time of the segments on the device (generate()'s)
+
+    def _params(self):
+        c = self.constraints
+        vmax, amax = np.asarray(c.max_velocity, np.float64), np.asarray(c.max_acceleration, np.float64)
+        dt = float(c.min_time_step)
+        # the reference divides by zero or never leaves its sampling loop on these
+        if not (np.all(np.isfinite(vmax)) and np.all(np.isfinite(amax)) and np.min(amax) > 0):
+            raise ValueError("constraints must be finite with min(max_acceleration) > 0")
+        if not (np.isfinite(dt) and dt > 0):
+            raise ValueError("min_time_step must be > 0")
+        return _lib.PolyTrajParams.make(vmax, amax, dt)
+
+    def _run(self, **kw):
+        if len(self.path) < 2:
+            raise ValueError("Need at least 2 waypoints for trajectory generation")
+        bc = np.array([[np.asarray(self.boundary_conditions[k], np.float64).reshape(3) for k in _BC_KEYS]])
+        r = batch.polytraj3d_batch([self.path], self._params(), bc=bc, **kw)
+        st = int(r["status"][0].item())
+        if st == _lib.STATUS_REF_RAISES:
+            raise ValueError("the path's total time is not finite")
+        if st != _lib.STATUS_FOUND:
+            raise _lib.PMPError(f"pmp_polytraj3d_batch status {st}")
+        return r
+
+    @staticmethod
+    def _rows(rows: np.ndarray) -> List[TrajectoryPoint]:
+        return [TrajectoryPoint(time=float(r[0]), position=r[1:4].copy(), velocity=r[4:7].copy(),
+                                acceleration=r[7:10].copy(), jerk=r[10:13].copy(),
+                                yaw=None if np.isnan(r[13]) else float(r[13]),
+                                yaw_rate=None if np.isnan(r[14]) else float(r[14])) for r in rows]
+
+    def generate(self) -> List[TrajectoryPoint]:
+        """generate() (:189-251): segment times, segments, sampling, yaw."""
+        r = self._run()
+        self.segment_times = [float(v) for v in r["segment_times"][: len(self.path) - 1].cpu().numpy()]
+        self.total_time = float(r["total_time"][0].item())
+        self._generated_total = self.total_time
+        self.trajectory_points = self._rows(r["points"][0, : int(r["n_points"][0].item())].cpu().numpy())
+        return self.trajectory_points
+
+    def _evaluate_many(self, ts) -> List[TrajectoryPoint]:
+        # evaluate(t) (:253-286) clips t to self.total_time -- which optimize_time_allocation() leaves
+        # scaled while the segments stay generate()'s: past their end the last segment's end is returned
+        tc = [float(np.clip(t, 0, self.total_time)) for t in ts]
+        pts = self._rows(self._run(eval_t=tc)["points"][0, : len(tc)].cpu().numpy())
+        for p, t in zip(pts, tc):
+            p.time = t
+        return pts
+
+    def evaluate(self, t: float) -> TrajectoryPoint:
+        if self._generated_total is None:
+            self.generate()
+        return self._evaluate_many([t])[0]
+
+    def resample(self, dt: float) -> List[TrajectoryPoint]:
+        """trajectory_base.py:193-216"""
+        if not self.trajectory_points:
+            self.generate()
+        if not dt > 0:
+            raise ValueError("dt must be > 0")
+        if self.total_time == self._generated_total:
+            r = self._run(sample_dt=float(dt))
+            return self._rows(r["points"][0, : int(r["n_points"][0].item())].cpu().numpy())
+        ts, t = [], 0.0  # after optimize_time_allocation(): the reference's loop over the scaled total_time
+        while t <= self.total_time:
+            ts.append(t)
+            t += dt
+        out = self._evaluate_many(ts)
+        if out[-1].time < self.total_time:
+            out += self._evaluate_many([self.total_time])
+        return out
+
+    def optimize_time_allocation(self, max_iterations: int = 10):
+        """:288-330, literally: generate() recomputes segment_times in every iteration, so the scaled times
+        survive only in segment_times / total_time after the call and the next generate() restores the
+        plain result."""
+        for _ in range(max_iterations):
+            self.generate()
+            if all(self.check_constraints().values()):
+                break
+            velocities = self.get_velocities()
+            accelerations = self.get_accelerations()
+            start = 0.0
+            for i, dur in enumerate(list(self.segment_times)):
+                a = int(start / self.constraints.min_time_step)
+                b = min(int((start + dur) / self.constraints.min_time_step), len(velocities) - 1)
+                if b > a:
+                    v_ratio = np.max(np.abs(velocities[a:b + 1]) / self.constraints.max_velocity)
+                    a_ratio = np.max(np.abs(accelerations[a:b + 1]) / self.constraints.max_acceleration)
+                    max_ratio = max(v_ratio, a_ratio)
+                    if max_ratio > 1.0:
+                        self.segment_times[i] *= (max_ratio ** 0.5)
+                start += dur
+        self.total_time = sum(self.segment_times)
+
+    # TrajectoryBase accessors (trajectory_base.py:120-149)
+    get_positions = TimeOptimalTrajectory3D.get_positions
+    get_velocities = TimeOptimalTrajectory3D.get_velocities
+    get_accelerations = TimeOptimalTrajectory3D.get_accelerations
+    get_times = TimeOptimalTrajectory3D.get_times
+    get_path_length = TimeOptimalTrajectory3D.get_path_length
+
+    def check_constraints(self) -> dict:
+        """trajectory_base.py:150-190, the jerk check included"""
+        res = TimeOptimalTrajectory3D.check_constraints(self)
+        if self.constraints.max_jerk is not None:
+            jerks = [tp.jerk for tp in self.trajectory_points if tp.jerk is not None]
+            if jerks and np.any(np.max(np.abs(np.array(jerks)), axis=0) > self.constraints.max_jerk):
+                res["jerk_satisfied"] = False
         return res
