@@ -680,6 +680,59 @@ int pmp_polytraj3d_batch(pmp_ctx* ctx, void* stream, const pmp_polytraj_params* 
 /* The largest max_waypoints pmp_polytraj3d_batch accepts (its LDS block beside the row stage). */
 int pmp_polytraj3d_max_waypoints(void);
 
+/* TrajectoryConstraints (trajectory/trajectory_base.py:30-45) as SplineTrajectory3D reads them, and its
+ * spline_degree (trajectory/spline_trajectory.py:16-32; the kernel clamps it to n - 1 per path) */
+typedef struct {
+    double max_velocity[3];
+    double max_acceleration[3];
+    double min_time_step;
+    int32_t spline_degree;
+    int32_t reserved;
+} pmp_splinetraj_params;
+
+/*
+ * Batched B-spline trajectories (the `spline` choice after 3D planning, examples/3d_example.py:100-133).
+ * Replaces SplineTrajectory3D(path, constraints, spline_degree, smoothing_factor=0).generate() /
+ * evaluate(t) / resample(dt) / reparameterize_constant_speed() (trajectory/spline_trajectory.py:16-392,
+ * trajectory_base.py:193-216): the centripetal parameter u (:60-77), k = min(spline_degree, n - 1), the
+ * interpolating spline UnivariateSpline(u, coords, k, s=0) returns (:79-120) -- FITPACK's knots for s = 0
+ * are k + 1 copies of u[0], u[(k+1)/2 : n-(k+1)/2] (odd k) or the midpoints (u[j] + u[j+1]) / 2,
+ * j = k/2 .. n-k/2-2 (even k), k + 1 copies of u[n-1]; the coefficients solve the banded collocation
+ * system, eliminated without pivoting -- its first and second derivative splines, the 500-sample time
+ * parameterisation (:154-203), sampling at t = 0, dt, ... by repeated addition through interp1d with the
+ * final point at rest (:216-263), _enforce_constraints' time scaling (:304-323), yaw / yaw rate on the
+ * scaled rows (trajectory_base.py:245-261).  Counts follow the reference's; values match it to rounding.
+ *   paths, one of two forms (the other's pointers NULL):
+ *     path_xyz [sum n][3] f64, path_off [nq + 1] i32   waypoints per path (reference order)
+ *     cells [nq][path_cap] i32, path_len [nq] i32, X, Y, Z   cell ids (x Y Z + y Z + z) as
+ *       pmp_graph3d_batch leaves them on the device, decoded in the order given
+ *   max_waypoints  >= every path's n (sizes LDS; 3 .. pmp_splinetraj3d_max_waypoints() = 500)
+ *   points [nq][point_cap][12]: time, position[3], velocity[3], acceleration[3], yaw, yaw rate
+ *       (NaN where the reference leaves None); n_points [nq]; total_time [nq] (after the scaling)
+ *   status [nq]  0 ok, 2 point_cap too small (the count is still reported; a path of more than 2^24
+ *                steps reports count 0), 3 more waypoints than max_waypoints (or path_cap), 4 the
+ *                reference raises (< 3 waypoints or an effective degree of 1: derivative(2) of a linear
+ *                spline; repeated consecutive waypoints: x must be strictly increasing if s = 0) or
+ *                never ends (total_time not finite)
+ *   eval_t [n_eval] nullable: instead of generate()'s rows, evaluate(t) (:273-302) at these times on the
+ *       scaled total_time (u = t / total_time; yaw / yaw rate NaN, as evaluate leaves them)
+ *   sample_dt  > 0: resample(sample_dt): evaluate at the repeated sum with this step; 0: generate()
+ *   constant_speed != 0: the rows reparameterize_constant_speed() (:325-392) leaves after generate(): the
+ *       1000-sample arc-length table, speed min(path_length / total_time, min(max_velocity)), the new
+ *       total_time, zero accelerations, no yaw
+ *   eval_t, sample_dt and constant_speed exclude each other.
+ * Refused with PMP_EINVAL (scipy raises, or the reference divides by zero or never leaves its loop):
+ * spline_degree outside 1..5, non-finite constraints, min|max_velocity| <= 0, min(max_acceleration) <= 0,
+ * min_time_step <= 0.  smoothing_factor > 0 (FITPACK's knot search) is not offered.
+ */
+int pmp_splinetraj3d_batch(pmp_ctx* ctx, void* stream, const pmp_splinetraj_params* prm, int nq,
+                           const double* path_xyz, const int32_t* path_off, const int32_t* cells,
+                           const int32_t* path_len, int path_cap, int X, int Y, int Z, int max_waypoints,
+                           int point_cap, double* points, int32_t* n_points, double* total_time, int32_t* status,
+                           const double* eval_t, int n_eval, double sample_dt, int constant_speed);
+/* The largest max_waypoints pmp_splinetraj3d_batch accepts (its LDS block within 64 KiB). */
+int pmp_splinetraj3d_max_waypoints(void);
+
 /* Launch-span recording for profiling: while set, every A* 2D launch of this context folds its
  * workers' first start and last end wall-clock ticks into span[0] (atomic min) and span[1] (atomic
  * max); the caller initialises span to {UINT64_MAX, 0}.  NULL switches it off. */

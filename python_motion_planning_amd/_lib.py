@@ -82,6 +82,9 @@ SIGNATURES = {
     "pmp_polytraj3d_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp,
                                   _vp, _vp, _vp, _i, ctypes.c_double]),
     "pmp_polytraj3d_max_waypoints": (_i, []),
+    "pmp_splinetraj3d_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
+                                    _vp, _i, ctypes.c_double, _i]),
+    "pmp_splinetraj3d_max_waypoints": (_i, []),
 }
 
 
@@ -172,6 +175,21 @@ class PolyTrajParams(ctypes.Structure):
     def make(cls, max_velocity=(2.0, 2.0, 2.0), max_acceleration=(1.0, 1.0, 1.0), min_time_step: float = 0.01):
         return cls((ctypes.c_double * 3)(*[float(v) for v in max_velocity]),
                    (ctypes.c_double * 3)(*[float(v) for v in max_acceleration]), float(min_time_step))
+
+
+class SplineTrajParams(ctypes.Structure):
+    """pmp_splinetraj_params == TrajectoryConstraints (trajectory/trajectory_base.py:30-45) max_velocity,
+    max_acceleration, min_time_step as SplineTrajectory3D reads them + its spline_degree
+    (trajectory/spline_trajectory.py:16-32; clamped to n - 1 per path by the kernel)."""
+    _fields_ = [("max_velocity", ctypes.c_double * 3), ("max_acceleration", ctypes.c_double * 3),
+                ("min_time_step", ctypes.c_double), ("spline_degree", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    @classmethod
+    def make(cls, max_velocity=(2.0, 2.0, 2.0), max_acceleration=(1.0, 1.0, 1.0), min_time_step: float = 0.01,
+             spline_degree: int = 5):
+        return cls((ctypes.c_double * 3)(*[float(v) for v in max_velocity]),
+                   (ctypes.c_double * 3)(*[float(v) for v in max_acceleration]), float(min_time_step),
+                   int(spline_degree), 0)
 
 
 TRACK_LQR, TRACK_MPC = 0, 1

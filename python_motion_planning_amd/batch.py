@@ -1060,3 +1060,102 @@ def polytraj3d_batch(paths, params, bc=None, point_cap: int | None = None, eval_
             for k in ("n_points", "total_time", "status"):
                 out[k][idx] = r[k]
     return out
+
+
+def splinetraj3d_batch(paths, params, point_cap: int | None = None, eval_t=None, sample_dt: float | None = None,
+                       constant_speed: bool = False, retry_overflow: bool = True, cells=None,
+                       max_waypoints: int | None = None):
+    """Batched SplineTrajectory3D(path, constraints, spline_degree).generate()
+    (trajectory/spline_trajectory.py:205-271, smoothing_factor = 0) on pmp_splinetraj3d_batch.  paths: list
+    of [n, 3] waypoint arrays (reference order), or None with cells=(path, path_len, (X, Y, Z)): the device
+    tensors a 3D grid planner returned (batch.astar3d_batch's "path", "path_len" and grid size), decoded
+    on the device.  params: _lib.SplineTrajParams.  With eval_t (1-D times), evaluate(t) (:273-302) at
+    those times instead of generate()'s rows; with sample_dt, resample(sample_dt)
+    (trajectory_base.py:193-216); with constant_speed, the rows reparameterize_constant_speed() (:325-392)
+    leaves.  The three exclude each other.
+    Returns dict of device tensors: points [nq, point_cap, 12] (time, position, velocity, acceleration,
+    yaw, yaw rate; NaN = None), n_points, total_time, status (include/pmp.h).  Paths whose points
+    overflow the first cap are re-run with their exact count when retry_overflow."""
+    torch = _lib.device_check()
+    L = _lib.load_library()
+    ctx = _lib.context()
+    wp_limit = int(L.pmp_splinetraj3d_max_waypoints())
+    dt = float(params.min_time_step) if sample_dt is None else float(sample_dt)
+    if sample_dt is not None and not dt > 0:
+        raise ValueError("sample_dt must be > 0")
+    if (eval_t is not None) + (sample_dt is not None) + bool(constant_speed) > 1:
+        raise ValueError("eval_t, sample_dt and constant_speed exclude each other")
+    et = None if eval_t is None else torch.as_tensor(np.asarray(eval_t, np.float64).ravel(), device="cuda")
+    n_eval = 0 if et is None else int(et.numel())
+    if cells is None:
+        arrs = [np.asarray(p, np.float64).reshape(-1, 3) for p in paths]
+        nq = len(arrs)
+        off = np.zeros(nq + 1, np.int32)
+        off[1:] = np.cumsum([len(a) for a in arrs])
+        nmax = max((len(a) for a in arrs), default=3)
+        src = (torch.as_tensor(np.concatenate(arrs) if nq else np.zeros((0, 3)), device="cuda"),
+               torch.as_tensor(off, device="cuda"))
+        path_cap, dims = 0, (0, 0, 0)
+        with np.errstate(all="ignore"):
+            lmax = max((float(np.sum(np.sqrt(np.sum(np.diff(a, axis=0) ** 2, axis=1)))) for a in arrs if len(a) > 1),
+                       default=0.0)
+    else:
+        cp, cl, dims = cells
+        cp = _dev(torch, cp, torch.int32)
+        cl = _dev(torch, cl, torch.int32).reshape(-1)
+        nq, path_cap = int(cp.shape[0]), int(cp.shape[1])
+        src = (cp, cl)
+        dims = tuple(int(v) for v in dims)
+        nmax = int(cl.max().item()) if max_waypoints is None and nq else 3
+        # neighbouring cells are at most sqrt(3) apart (any-angle paths may overflow: retried)
+        lmax = (max(nmax, int(max_waypoints or 0)) - 1) * 3.0 ** 0.5
+    nmax = int(max_waypoints) if max_waypoints is not None else min(max(3, nmax), wp_limit)
+    if point_cap is None:
+        if et is not None:
+            point_cap = n_eval + 1
+        else:
+            # total_time is about the curve's length over min|max_velocity| (one unit of u for a short curve);
+            # the scaling of _enforce_constraints can stretch it: such paths are retried
+            vclip = min(abs(v) for v in params.max_velocity)
+            est = max(1.5 * lmax / vclip, 2.0) / dt if vclip > 0 and dt > 0 and np.isfinite(lmax) else 2048.0
+            point_cap = int(min(est, float(1 << 24))) + 3 if np.isfinite(est) else 2048
+
+    def launch(a, b, pc):
+        m = int(b.shape[0]) - 1 if cells is None else int(b.shape[0])
+        f64 = dict(dtype=torch.float64, device="cuda")
+        i32 = dict(dtype=torch.int32, device="cuda")
+        o = dict(points=torch.empty((m, pc, 12), **f64), n_points=torch.empty(m, **i32), total_time=torch.empty(m, **f64),
+                 status=torch.empty(m, **i32))
+        if cells is None:
+            args = (a.data_ptr(), b.data_ptr(), None, None, 0, 0, 0, 0)
+        else:
+            args = (None, None, a.data_ptr(), b.data_ptr(), path_cap) + dims
+        rc = L.pmp_splinetraj3d_batch(ctx, _lib.stream_ptr(), ctypes.byref(params), m, *args, nmax, pc,
+                                      o["points"].data_ptr(), o["n_points"].data_ptr(), o["total_time"].data_ptr(),
+                                      o["status"].data_ptr(), _lib.ptr(et), n_eval, 0.0 if sample_dt is None else dt,
+                                      1 if constant_speed else 0)
+        _lib.check(ctx, rc, "pmp_splinetraj3d_batch")
+        return o
+
+    out = launch(src[0], src[1], int(point_cap))
+    if retry_overflow and nq:
+        st = out["status"].cpu().numpy()
+        npt = out["n_points"].cpu().numpy()
+        redo = np.nonzero((st == _lib.STATUS_PATH_OVERFLOW) & (npt > point_cap))[0]
+        if len(redo):
+            pc = int(npt[redo].max())
+            idx = torch.as_tensor(redo, device="cuda", dtype=torch.long)
+            if cells is None:
+                sub = [arrs[i] for i in redo]
+                so = np.zeros(len(sub) + 1, np.int32)
+                so[1:] = np.cumsum([len(a) for a in sub])
+                r = launch(torch.as_tensor(np.concatenate(sub), device="cuda"), torch.as_tensor(so, device="cuda"), pc)
+            else:
+                r = launch(src[0][idx].contiguous(), src[1][idx].contiguous(), pc)
+            big = torch.full((nq, pc, 12), float("nan"), dtype=torch.float64, device="cuda")
+            big[:, : int(point_cap)] = out["points"]
+            big[idx] = r["points"]
+            out["points"] = big
+            for k in ("n_points", "total_time", "status"):
+                out[k][idx] = r[k]
+    return out

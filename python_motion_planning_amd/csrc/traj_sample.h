@@ -1,5 +1,5 @@
 // The sampling loop's time stepping and the yaw / yaw-rate tail shared by the trajectory kernels
-// (totp3d.hip, polytraj3d.hip): generate() / resample() step t = 0, dt, ... by repeated addition and
+// (totp3d.hip, polytraj3d.hip, splinetraj3d.hip): generate() / resample() step t = 0, dt, ... by repeated addition and
 // append total_time when the last step falls short of it (time_optimal_trajectory.py:260-302,
 // polynomial_trajectory.py:238-246, trajectory_base.py:193-216); compute_yaw_from_velocity
 // (trajectory_base.py:245-261) sets yaw where the planar speed exceeds 1e-6 and the yaw rate where
@@ -9,10 +9,13 @@
 
 // Lane 0 only: the next (up to 64) query times into tq, meta[0] = how many, meta[1] = last round.
 // eval_t: these times instead (count = how many were taken in earlier rounds).  t / last_t carry the
-// reference's accumulated time (`t += dt`; k * dt rounds differently) across rounds.
+// reference's accumulated time (`t += dt`; k * dt rounds differently) across rounds.  appended (nullable):
+// set to whether this round's last time is the total_time the reference appends after its loop.
 __device__ __forceinline__ void traj_next_times(const double* __restrict__ eval_t, int n_eval, int count, double dt,
-                                                double total, double& t, double& last_t, double* tq, int* meta)
+                                                double total, double& t, double& last_t, double* tq, int* meta,
+                                                bool* appended = nullptr)
 {
+    if (appended) *appended = false;
     int k = 0;
     bool fin = false;
     if (eval_t) {
@@ -28,6 +31,7 @@ __device__ __forceinline__ void traj_next_times(const double* __restrict__ eval_
                 if (count + k > 0 && last_t < total) {
                     tq[k++] = total;
                     last_t = total;
+                    if (appended) *appended = true;
                 }
                 fin = true;
                 break;

@@ -8,6 +8,10 @@ evaluate() run on the GPU.  For many paths at once use batch.totp3d_batch.
 
 Drop-in PolynomialTrajectory3D (trajectory/polynomial_trajectory.py:52-331, the example's `polynomial`
 choice, examples/3d_example.py:112-117) on pmp_polytraj3d_batch, batched by batch.polytraj3d_batch.
+
+Drop-in SplineTrajectory3D (trajectory/spline_trajectory.py:8-392, the example's `spline` choice,
+examples/3d_example.py:118-123) for smoothing_factor = 0 on pmp_splinetraj3d_batch, batched by
+batch.splinetraj3d_batch.
 """
 from __future__ import annotations
 
@@ -291,3 +295,130 @@ class PolynomialTrajectory3D:
             if jerks and np.any(np.max(np.abs(np.array(jerks)), axis=0) > self.constraints.max_jerk):
                 res["jerk_satisfied"] = False
         return res
+
+
+class SplineTrajectory3D:
+    """spline_trajectory.py:8-392 (B-splines through the waypoints, time-scaled to the constraints) on
+    pmp_splinetraj3d_batch: generate(), evaluate(), resample() and reparameterize_constant_speed() run on
+    the GPU.  smoothing_factor > 0 (FITPACK's knot search) is not offered.  For many paths at once use
+    batch.splinetraj3d_batch."""
+
+    def __init__(self, path, constraints: Optional[TrajectoryConstraints] = None, spline_degree: int = 5,
+                 smoothing_factor: float = 0.0):
+        if not path:
+            raise ValueError("Path cannot be empty")
+        if smoothing_factor > 0:
+            raise NotImplementedError("smoothing_factor > 0 (FITPACK's smoothing knot search) is not offered; "
+                                      "smoothing_factor = 0 interpolates the waypoints")
+        # _process_path (trajectory_base.py:79-95): 2D points get z = 0
+        self.dimension = 3
+        self.path = np.array([[p[0], p[1], 0.0] if len(p) == 2 else list(p) for p in path], dtype=float)
+        if constraints is None:
+            constraints = TrajectoryConstraints(np.array([2.0] * 3), np.array([1.0] * 3))
+        self.constraints = constraints
+        self.trajectory_points: List[TrajectoryPoint] = []
+        self.total_time = 0.0
+        self.segment_times: List[float] = []
+        self.spline_degree = min(spline_degree, len(path) - 1)
+        self.smoothing_factor = smoothing_factor
+        self.u_waypoints = None
+        self.u_max = 1.0
+        self._generated_total = None  # total_time of the spline's time scale on the device (generate()'s)
+
+    def _params(self):
+        """Everything the reference raises on, or never returns from, before any device call."""
+        c = self.constraints
+        vmax, amax = np.asarray(c.max_velocity, np.float64), np.asarray(c.max_acceleration, np.float64)
+        dt = float(c.min_time_step)
+        n = len(self.path)
+        if n < 3:
+            raise ValueError("Need at least 3 waypoints: the second derivative of a linear spline does not exist")
+        if not 1 <= self.spline_degree <= 5:
+            raise ValueError("k should be 1 <= k <= 5")
+        if self.spline_degree < 2:
+            raise ValueError("spline_degree 1: the second derivative of a linear spline does not exist")
+        if np.any(np.all(self.path[1:] == self.path[:-1], axis=1)):
+            raise ValueError("x must be strictly increasing if s = 0 (two consecutive waypoints are equal)")
+        if not (np.all(np.isfinite(vmax)) and np.all(np.isfinite(amax)) and np.min(np.abs(vmax)) > 0 and np.min(amax) > 0):
+            raise ValueError("constraints must be finite with min|max_velocity| > 0 and min(max_acceleration) > 0")
+        if not (np.isfinite(dt) and dt > 0):
+            raise ValueError("min_time_step must be > 0")
+        return _lib.SplineTrajParams.make(vmax, amax, dt, self.spline_degree)
+
+    def _run(self, **kw):
+        r = batch.splinetraj3d_batch([self.path], self._params(), **kw)
+        st = int(r["status"][0].item())
+        if st == _lib.STATUS_REF_RAISES:
+            raise ValueError("x must be strictly increasing if s = 0, or the path's total time is not finite")
+        if st != _lib.STATUS_FOUND:
+            raise _lib.PMPError(f"pmp_splinetraj3d_batch status {st}")
+        return r
+
+    def _compute_centripetal_parameterization(self) -> np.ndarray:
+        """:60-77"""
+        d = np.zeros(len(self.path))
+        for i in range(1, len(self.path)):
+            d[i] = d[i - 1] + np.sqrt(np.linalg.norm(self.path[i] - self.path[i - 1]))
+        return d / d[-1] if d[-1] > 0 else np.linspace(0, 1, len(self.path))
+
+    def generate(self) -> List[TrajectoryPoint]:
+        """generate() (:205-271): fit, time parameterisation, sampling, _enforce_constraints, yaw."""
+        r = self._run()
+        self.u_waypoints = self._compute_centripetal_parameterization()
+        self.total_time = float(r["total_time"][0].item())
+        self._generated_total = self.total_time
+        self.trajectory_points = _points(r["points"][0, : int(r["n_points"][0].item())].cpu().numpy())
+        return self.trajectory_points
+
+    def _evaluate_many(self, ts) -> List[TrajectoryPoint]:
+        # evaluate(t) (:273-302) divides by self.total_time, which reparameterize_constant_speed() replaces
+        # while the spline stays generate()'s: the device then evaluates at t total_gen / total_time and the
+        # chain-rule factors are corrected here (u agrees to rounding)
+        tc = [float(np.clip(t, 0, self.total_time)) for t in ts]
+        k = 1.0 if self.total_time == self._generated_total else self._generated_total / self.total_time
+        pts = _points(self._run(eval_t=[t * k for t in tc])["points"][0, : len(tc)].cpu().numpy(), with_yaw=False)
+        for p, t in zip(pts, tc):
+            p.time = t
+            if k != 1.0:
+                p.velocity *= k
+                p.acceleration *= k * k
+        return pts
+
+    def evaluate(self, t: float) -> TrajectoryPoint:
+        if self._generated_total is None:
+            self.generate()
+        return self._evaluate_many([t])[0]
+
+    def resample(self, dt: float) -> List[TrajectoryPoint]:
+        """trajectory_base.py:193-216"""
+        if not self.trajectory_points:
+            self.generate()
+        if not dt > 0:
+            raise ValueError("dt must be > 0")
+        if self.total_time == self._generated_total:
+            r = self._run(sample_dt=float(dt))
+            return _points(r["points"][0, : int(r["n_points"][0].item())].cpu().numpy(), with_yaw=False)
+        ts, t = [], 0.0
+        while t <= self.total_time:
+            ts.append(t)
+            t += dt
+        out = self._evaluate_many(ts)
+        if out[-1].time < self.total_time:
+            out += self._evaluate_many([self.total_time])
+        return out
+
+    def reparameterize_constant_speed(self):
+        """:325-392, on generate()'s spline and total_time"""
+        if self._generated_total is None:
+            self.generate()
+        r = self._run(constant_speed=True)
+        self.total_time = float(r["total_time"][0].item())
+        self.trajectory_points = _points(r["points"][0, : int(r["n_points"][0].item())].cpu().numpy(), with_yaw=False)
+
+    # TrajectoryBase accessors (trajectory_base.py:120-191)
+    get_positions = TimeOptimalTrajectory3D.get_positions
+    get_velocities = TimeOptimalTrajectory3D.get_velocities
+    get_accelerations = TimeOptimalTrajectory3D.get_accelerations
+    get_times = TimeOptimalTrajectory3D.get_times
+    get_path_length = TimeOptimalTrajectory3D.get_path_length
+    check_constraints = TimeOptimalTrajectory3D.check_constraints
