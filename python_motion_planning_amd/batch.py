@@ -886,6 +886,89 @@ def lpastar3d_batch(occ, starts, goals, changes=None, heuristic: str = "euclidea
     return out
 
 
+def _xyz_arrays(paths):
+    return [np.asarray(p, np.float64).reshape(-1, 3) for p in paths]
+
+
+def _traj3d_batch(torch, arrs, cells, row, min_wp, wp_limit, max_waypoints, eval_t, point_cap, estimate, call,
+                  retry_overflow, merge=(), per_path=None):
+    """What totp3d_batch, polytraj3d_batch and splinetraj3d_batch share: the two path sources, the eval_t
+    upload, the common outputs and the overflow retry.
+    arrs: list of [n, 3] f64 arrays (_xyz_arrays), packed to (flat [sum n, 3], off [nq + 1] i32); or None
+    with cells=(path [nq, path_cap], path_len, (X, Y, Z)).  row: doubles per point.  The launch's max_waypoints is
+    the one given, else the longest path's, at least min_wp and at most wp_limit (None: no limit).
+    estimate(arrs, wp) -> the first point_cap when none is given and there is no eval_t (arrs: the waypoint
+    arrays, or None in the cells form, where no path has more than wp waypoints).
+    call(o, a, src, nmax, ev, pp) adds the kind's outputs to o (points [m, pc, row], n_points, total_time,
+    status) and launches its C entry on m paths: a is the path tensor, src the entry's eight path-source
+    arguments (path_xyz, path_off, cells, path_len, path_cap, X, Y, Z), nmax its max_waypoints, ev its
+    (eval_t, n_eval), pp the per_path inputs {name: (array or None, shape of one path's)} as f64 device
+    tensors of those m paths.
+    Paths whose points overflow the first cap are run again with the largest count among them: their rows,
+    n_points, total_time, status and the outputs named in merge replace the first run's; points grows to that
+    count, NaN where the first run had no row.  Returns (out, off): off is the host offsets, None in the
+    cells form."""
+    et = None if eval_t is None else torch.as_tensor(np.asarray(eval_t, np.float64).ravel(), device="cuda")
+    ev = (_lib.ptr(et), 0 if et is None else int(et.numel()))
+
+    def pack(arrs):
+        off = np.zeros(len(arrs) + 1, np.int32)
+        off[1:] = np.cumsum([len(a) for a in arrs])
+        flat = torch.as_tensor(np.concatenate(arrs) if arrs else np.zeros((0, 3)), device="cuda")
+        return flat, torch.as_tensor(off, device="cuda"), off
+
+    if cells is None:
+        nq = len(arrs)
+        a, b, off = pack(arrs)
+        tail = (0, 0, 0, 0)
+        wp = max((len(p) for p in arrs), default=min_wp)
+    else:
+        off = None
+        a = _dev(torch, cells[0], torch.int32)
+        b = _dev(torch, cells[1], torch.int32).reshape(-1)
+        nq = int(a.shape[0])
+        tail = (int(a.shape[1]),) + tuple(int(v) for v in cells[2])
+        wp = int(b.max().item()) if max_waypoints is None and nq else min_wp
+    if max_waypoints is not None:
+        nmax = int(max_waypoints)
+    else:
+        nmax = max(min_wp, wp) if wp_limit is None else min(max(min_wp, wp), wp_limit)
+    if point_cap is None:
+        point_cap = ev[1] + 1 if et is not None else estimate(arrs, max(wp, int(max_waypoints or 0)))
+    point_cap = int(point_cap)
+    pp = {k: None if v is None else _dev(torch, v, torch.float64).reshape((nq,) + shape)
+          for k, (v, shape) in (per_path or {}).items()}
+
+    def launch(a, b, pp, pc):
+        m = int(b.shape[0]) - 1 if cells is None else int(b.shape[0])
+        f64 = dict(dtype=torch.float64, device="cuda")
+        i32 = dict(dtype=torch.int32, device="cuda")
+        o = dict(points=torch.empty((m, pc, row), **f64), n_points=torch.empty(m, **i32),
+                 total_time=torch.empty(m, **f64), status=torch.empty(m, **i32))
+        ptrs = (a.data_ptr(), b.data_ptr())
+        src = (ptrs + (None, None) if cells is None else (None, None) + ptrs) + tail
+        call(o, a, src, nmax, ev, pp)
+        return o
+
+    out = launch(a, b, pp, point_cap)
+    if retry_overflow and nq:
+        st = out["status"].cpu().numpy()
+        npt = out["n_points"].cpu().numpy()
+        redo = np.nonzero((st == _lib.STATUS_PATH_OVERFLOW) & (npt > point_cap))[0]
+        if len(redo):
+            pc = int(npt[redo].max())
+            idx = torch.as_tensor(redo, device="cuda", dtype=torch.long)
+            sa, sb = pack([arrs[i] for i in redo])[:2] if cells is None else (a[idx].contiguous(), b[idx].contiguous())
+            r = launch(sa, sb, {k: None if v is None else v[idx].contiguous() for k, v in pp.items()}, pc)
+            big = torch.full((nq, pc, row), float("nan"), dtype=torch.float64, device="cuda")
+            big[:, :point_cap] = out["points"]
+            big[idx] = r["points"]
+            out["points"] = big
+            for k in ("n_points", "total_time", "status") + tuple(merge):
+                out[k][idx] = r[k]
+    return out, off
+
+
 def totp3d_batch(paths, params, point_cap: int | None = None, eval_t=None, retry_overflow: bool = True):
     """Batched TimeOptimalTrajectory3D(path, constraints, path_resolution).generate()
     (trajectory/time_optimal_trajectory.py:260-302) on pmp_totp3d_batch.  paths: list of [n, 3]
@@ -898,59 +981,28 @@ def totp3d_batch(paths, params, point_cap: int | None = None, eval_t=None, retry
     torch = _lib.device_check()
     L = _lib.load_library()
     ctx = _lib.context()
-    arrs = [np.asarray(p, np.float64).reshape(-1, 3) for p in paths]
-    nq = len(arrs)
-    off = np.zeros(nq + 1, np.int32)
-    off[1:] = np.cumsum([len(a) for a in arrs])
-    nmax = max(2, max((len(a) for a in arrs), default=2))
+    arrs = _xyz_arrays(paths)
     # n_samples = max(int(L / res), 100) with L summed in the kernel's (the reference's) order
     res = float(params.path_resolution)
     ns = [max(int(np.cumsum(np.sqrt(np.sum(np.diff(a, axis=0) ** 2, axis=1)))[-1] / res), 100) if len(a) > 1 else 1
           for a in arrs]
     sample_cap = max(ns, default=1) + 1
-    flat = torch.as_tensor(np.concatenate(arrs) if nq else np.zeros((0, 3)), device="cuda")
-    off_d = torch.as_tensor(off, device="cuda")
-    et = None if eval_t is None else torch.as_tensor(np.asarray(eval_t, np.float64).ravel(), device="cuda")
-    n_eval = 0 if et is None else int(et.numel())
-    if point_cap is None:
-        point_cap = n_eval + 1 if et is not None else 2048
+    profiles = ("s_values", "s_dot", "s_ddot", "time")
 
-    def launch(idx_paths, offs, pc):
-        m = len(offs) - 1
-        f64 = dict(dtype=torch.float64, device="cuda")
-        i32 = dict(dtype=torch.int32, device="cuda")
-        o = dict(s_values=torch.empty((m, sample_cap), **f64), s_dot=torch.empty((m, sample_cap), **f64),
-                 s_ddot=torch.empty((m, sample_cap), **f64), time=torch.empty((m, sample_cap), **f64),
-                 n_samples=torch.empty(m, **i32), points=torch.empty((m, pc, 12), **f64), n_points=torch.empty(m, **i32),
-                 total_time=torch.empty(m, **f64), status=torch.empty(m, **i32))
+    def call(o, a, src, nmax, ev, pp):
+        m, pc = o["points"].shape[:2]
+        for k in profiles:
+            o[k] = torch.empty((m, sample_cap), dtype=torch.float64, device="cuda")
+        o["n_samples"] = torch.empty(m, dtype=torch.int32, device="cuda")
         if m:
-            rc = L.pmp_totp3d_batch(ctx, _lib.stream_ptr(), ctypes.byref(params), m, idx_paths.data_ptr(),
-                                    offs.data_ptr(), nmax, sample_cap, o["s_values"].data_ptr(), o["s_dot"].data_ptr(),
-                                    o["s_ddot"].data_ptr(), o["time"].data_ptr(), o["n_samples"].data_ptr(), pc,
-                                    o["points"].data_ptr(), o["n_points"].data_ptr(), o["total_time"].data_ptr(),
-                                    o["status"].data_ptr(), _lib.ptr(et), n_eval)
+            rc = L.pmp_totp3d_batch(ctx, _lib.stream_ptr(), ctypes.byref(params), m, *src[:2], nmax, sample_cap,
+                                    o["s_values"].data_ptr(), o["s_dot"].data_ptr(), o["s_ddot"].data_ptr(),
+                                    o["time"].data_ptr(), o["n_samples"].data_ptr(), pc, o["points"].data_ptr(),
+                                    o["n_points"].data_ptr(), o["total_time"].data_ptr(), o["status"].data_ptr(), *ev)
             _lib.check(ctx, rc, "pmp_totp3d_batch")
-        return o
 
-    out = launch(flat, off_d, int(point_cap))
-    if retry_overflow and nq:
-        st = out["status"].cpu().numpy()
-        npt = out["n_points"].cpu().numpy()
-        redo = np.nonzero((st == _lib.STATUS_PATH_OVERFLOW) & (npt > point_cap))[0]
-        if len(redo):
-            pc = int(npt[redo].max())
-            sub = [arrs[i] for i in redo]
-            so = np.zeros(len(sub) + 1, np.int32)
-            so[1:] = np.cumsum([len(a) for a in sub])
-            r = launch(torch.as_tensor(np.concatenate(sub), device="cuda"), torch.as_tensor(so, device="cuda"), pc)
-            big = torch.full((nq, pc, 12), float("nan"), dtype=torch.float64, device="cuda")
-            big[:, : int(point_cap)] = out["points"]
-            idx = torch.as_tensor(redo, device="cuda", dtype=torch.long)
-            big[idx] = r["points"]
-            out["points"] = big
-            for k in ("s_values", "s_dot", "s_ddot", "time", "n_samples", "n_points", "total_time", "status"):
-                out[k][idx] = r[k]
-    return out
+    return _traj3d_batch(torch, arrs, None, 12, 2, None, None, eval_t, point_cap, lambda arrs, wp: 2048, call,
+                         retry_overflow, merge=profiles + ("n_samples",))[0]
 
 
 def polytraj_segment_times(path, params):
@@ -982,83 +1034,34 @@ def polytraj3d_batch(paths, params, bc=None, point_cap: int | None = None, eval_
     dt = float(params.min_time_step) if sample_dt is None else float(sample_dt)
     if sample_dt is not None and not dt > 0:
         raise ValueError("sample_dt must be > 0")
-    et = None if eval_t is None else torch.as_tensor(np.asarray(eval_t, np.float64).ravel(), device="cuda")
-    n_eval = 0 if et is None else int(et.numel())
-    tmax = None  # an upper bound of the batch's total_time
-    if cells is None:
-        arrs = [np.asarray(p, np.float64).reshape(-1, 3) for p in paths]
-        nq = len(arrs)
-        off = np.zeros(nq + 1, np.int32)
-        off[1:] = np.cumsum([len(a) for a in arrs])
-        nmax = max((len(a) for a in arrs), default=2)
-        src = (torch.as_tensor(np.concatenate(arrs) if nq else np.zeros((0, 3)), device="cuda"),
-               torch.as_tensor(off, device="cuda"))
-        path_cap, dims = 0, (0, 0, 0)
-        if np.isfinite(dt) and dt > 0 and min(params.max_acceleration) > 0:
+
+    def estimate(arrs, wp):
+        # an upper bound of the batch's total_time over the step
+        if not (np.isfinite(dt) and dt > 0 and min(params.max_acceleration) > 0):
+            return 2048
+        if arrs is None:  # neighbouring cells are at most sqrt(3) apart (any-angle paths may overflow: retried)
+            tmax = (wp - 1) * float(polytraj_segment_times([[0, 0, 0], [1, 1, 1]], params)[0])
+        else:
             with np.errstate(all="ignore"):
                 tmax = max((float(np.sum(polytraj_segment_times(a, params))) for a in arrs if len(a) > 1), default=0.0)
-    else:
-        cp, cl, dims = cells
-        cp = _dev(torch, cp, torch.int32)
-        cl = _dev(torch, cl, torch.int32).reshape(-1)
-        nq, path_cap = int(cp.shape[0]), int(cp.shape[1])
-        src = (cp, cl)
-        dims = tuple(int(v) for v in dims)
-        nmax = int(cl.max().item()) if max_waypoints is None and nq else 2
-        if np.isfinite(dt) and dt > 0 and min(params.max_acceleration) > 0:
-            # neighbouring cells are at most sqrt(3) apart (any-angle paths may overflow: retried)
-            tmax = (max(nmax, int(max_waypoints or 0)) - 1) * float(polytraj_segment_times([[0, 0, 0], [1, 1, 1]], params)[0])
-    nmax = int(max_waypoints) if max_waypoints is not None else min(max(2, nmax), wp_limit)
-    if point_cap is None:
-        if et is not None:
-            point_cap = n_eval + 1
-        else:
-            point_cap = int(min(tmax / dt, float(1 << 24))) + 3 if tmax is not None and np.isfinite(tmax) else 2048
-    bcd = None if bc is None else _dev(torch, bc, torch.float64).reshape(nq, 4, 3)
+        return int(min(tmax / dt, float(1 << 24))) + 3 if np.isfinite(tmax) else 2048
 
-    def launch(a, b, bcs, pc):
-        m = int(b.shape[0]) - 1 if cells is None else int(b.shape[0])
-        f64 = dict(dtype=torch.float64, device="cuda")
-        i32 = dict(dtype=torch.int32, device="cuda")
-        o = dict(points=torch.empty((m, pc, 15), **f64), n_points=torch.empty(m, **i32), total_time=torch.empty(m, **f64),
-                 status=torch.empty(m, **i32),
-                 segment_times=torch.zeros(int(a.shape[0]) if cells is None else (m, path_cap), **f64))
-        if cells is None:
-            args = (a.data_ptr(), b.data_ptr(), None, None, 0, 0, 0, 0)
-        else:
-            args = (None, None, a.data_ptr(), b.data_ptr(), path_cap) + dims
-        rc = L.pmp_polytraj3d_batch(ctx, _lib.stream_ptr(), ctypes.byref(params), m, *args, _lib.ptr(bcs), nmax, pc,
+    def call(o, a, src, nmax, ev, pp):
+        m, pc = o["points"].shape[:2]
+        # segment_times is not merged after a retry: it depends on the waypoints alone
+        o["segment_times"] = torch.zeros(int(a.shape[0]) if cells is None else tuple(a.shape), dtype=torch.float64,
+                                         device="cuda")
+        rc = L.pmp_polytraj3d_batch(ctx, _lib.stream_ptr(), ctypes.byref(params), m, *src, _lib.ptr(pp["bc"]), nmax, pc,
                                     o["points"].data_ptr(), o["n_points"].data_ptr(), o["total_time"].data_ptr(),
-                                    o["segment_times"].data_ptr(), o["status"].data_ptr(), _lib.ptr(et), n_eval,
+                                    o["segment_times"].data_ptr(), o["status"].data_ptr(), *ev,
                                     0.0 if sample_dt is None else dt)
         _lib.check(ctx, rc, "pmp_polytraj3d_batch")
-        return o
 
-    out = launch(src[0], src[1], bcd, int(point_cap))
+    out, off = _traj3d_batch(torch, _xyz_arrays(paths) if cells is None else None, cells, 15, 2, wp_limit,
+                             max_waypoints, eval_t, point_cap, estimate, call, retry_overflow,
+                             per_path=dict(bc=(bc, (4, 3))))
     if cells is None:
         out["seg_off"] = off
-    if retry_overflow and nq:
-        st = out["status"].cpu().numpy()
-        npt = out["n_points"].cpu().numpy()
-        redo = np.nonzero((st == _lib.STATUS_PATH_OVERFLOW) & (npt > point_cap))[0]
-        if len(redo):
-            pc = int(npt[redo].max())
-            idx = torch.as_tensor(redo, device="cuda", dtype=torch.long)
-            if cells is None:
-                sub = [arrs[i] for i in redo]
-                so = np.zeros(len(sub) + 1, np.int32)
-                so[1:] = np.cumsum([len(a) for a in sub])
-                r = launch(torch.as_tensor(np.concatenate(sub), device="cuda"), torch.as_tensor(so, device="cuda"),
-                           None if bcd is None else bcd[idx].contiguous(), pc)
-            else:
-                r = launch(src[0][idx].contiguous(), src[1][idx].contiguous(),
-                           None if bcd is None else bcd[idx].contiguous(), pc)
-            big = torch.full((nq, pc, 15), float("nan"), dtype=torch.float64, device="cuda")
-            big[:, : int(point_cap)] = out["points"]
-            big[idx] = r["points"]
-            out["points"] = big
-            for k in ("n_points", "total_time", "status"):
-                out[k][idx] = r[k]
     return out
 
 
@@ -1085,77 +1088,27 @@ def splinetraj3d_batch(paths, params, point_cap: int | None = None, eval_t=None,
         raise ValueError("sample_dt must be > 0")
     if (eval_t is not None) + (sample_dt is not None) + bool(constant_speed) > 1:
         raise ValueError("eval_t, sample_dt and constant_speed exclude each other")
-    et = None if eval_t is None else torch.as_tensor(np.asarray(eval_t, np.float64).ravel(), device="cuda")
-    n_eval = 0 if et is None else int(et.numel())
-    if cells is None:
-        arrs = [np.asarray(p, np.float64).reshape(-1, 3) for p in paths]
-        nq = len(arrs)
-        off = np.zeros(nq + 1, np.int32)
-        off[1:] = np.cumsum([len(a) for a in arrs])
-        nmax = max((len(a) for a in arrs), default=3)
-        src = (torch.as_tensor(np.concatenate(arrs) if nq else np.zeros((0, 3)), device="cuda"),
-               torch.as_tensor(off, device="cuda"))
-        path_cap, dims = 0, (0, 0, 0)
-        with np.errstate(all="ignore"):
-            lmax = max((float(np.sum(np.sqrt(np.sum(np.diff(a, axis=0) ** 2, axis=1)))) for a in arrs if len(a) > 1),
-                       default=0.0)
-    else:
-        cp, cl, dims = cells
-        cp = _dev(torch, cp, torch.int32)
-        cl = _dev(torch, cl, torch.int32).reshape(-1)
-        nq, path_cap = int(cp.shape[0]), int(cp.shape[1])
-        src = (cp, cl)
-        dims = tuple(int(v) for v in dims)
-        nmax = int(cl.max().item()) if max_waypoints is None and nq else 3
-        # neighbouring cells are at most sqrt(3) apart (any-angle paths may overflow: retried)
-        lmax = (max(nmax, int(max_waypoints or 0)) - 1) * 3.0 ** 0.5
-    nmax = int(max_waypoints) if max_waypoints is not None else min(max(3, nmax), wp_limit)
-    if point_cap is None:
-        if et is not None:
-            point_cap = n_eval + 1
-        else:
-            # total_time is about the curve's length over min|max_velocity| (one unit of u for a short curve);
-            # the scaling of _enforce_constraints can stretch it: such paths are retried
-            vclip = min(abs(v) for v in params.max_velocity)
-            est = max(1.5 * lmax / vclip, 2.0) / dt if vclip > 0 and dt > 0 and np.isfinite(lmax) else 2048.0
-            point_cap = int(min(est, float(1 << 24))) + 3 if np.isfinite(est) else 2048
 
-    def launch(a, b, pc):
-        m = int(b.shape[0]) - 1 if cells is None else int(b.shape[0])
-        f64 = dict(dtype=torch.float64, device="cuda")
-        i32 = dict(dtype=torch.int32, device="cuda")
-        o = dict(points=torch.empty((m, pc, 12), **f64), n_points=torch.empty(m, **i32), total_time=torch.empty(m, **f64),
-                 status=torch.empty(m, **i32))
-        if cells is None:
-            args = (a.data_ptr(), b.data_ptr(), None, None, 0, 0, 0, 0)
+    def estimate(arrs, wp):
+        if arrs is None:  # neighbouring cells are at most sqrt(3) apart (any-angle paths may overflow: retried)
+            lmax = (wp - 1) * 3.0 ** 0.5
         else:
-            args = (None, None, a.data_ptr(), b.data_ptr(), path_cap) + dims
-        rc = L.pmp_splinetraj3d_batch(ctx, _lib.stream_ptr(), ctypes.byref(params), m, *args, nmax, pc,
+            with np.errstate(all="ignore"):
+                lmax = max((float(np.sum(np.sqrt(np.sum(np.diff(a, axis=0) ** 2, axis=1)))) for a in arrs if len(a) > 1),
+                           default=0.0)
+        # total_time is about the curve's length over min|max_velocity| (one unit of u for a short curve);
+        # the scaling of _enforce_constraints can stretch it: such paths are retried
+        vclip = min(abs(v) for v in params.max_velocity)
+        est = max(1.5 * lmax / vclip, 2.0) / dt if vclip > 0 and dt > 0 and np.isfinite(lmax) else 2048.0
+        return int(min(est, float(1 << 24))) + 3 if np.isfinite(est) else 2048
+
+    def call(o, a, src, nmax, ev, pp):
+        m, pc = o["points"].shape[:2]
+        rc = L.pmp_splinetraj3d_batch(ctx, _lib.stream_ptr(), ctypes.byref(params), m, *src, nmax, pc,
                                       o["points"].data_ptr(), o["n_points"].data_ptr(), o["total_time"].data_ptr(),
-                                      o["status"].data_ptr(), _lib.ptr(et), n_eval, 0.0 if sample_dt is None else dt,
+                                      o["status"].data_ptr(), *ev, 0.0 if sample_dt is None else dt,
                                       1 if constant_speed else 0)
         _lib.check(ctx, rc, "pmp_splinetraj3d_batch")
-        return o
 
-    out = launch(src[0], src[1], int(point_cap))
-    if retry_overflow and nq:
-        st = out["status"].cpu().numpy()
-        npt = out["n_points"].cpu().numpy()
-        redo = np.nonzero((st == _lib.STATUS_PATH_OVERFLOW) & (npt > point_cap))[0]
-        if len(redo):
-            pc = int(npt[redo].max())
-            idx = torch.as_tensor(redo, device="cuda", dtype=torch.long)
-            if cells is None:
-                sub = [arrs[i] for i in redo]
-                so = np.zeros(len(sub) + 1, np.int32)
-                so[1:] = np.cumsum([len(a) for a in sub])
-                r = launch(torch.as_tensor(np.concatenate(sub), device="cuda"), torch.as_tensor(so, device="cuda"), pc)
-            else:
-                r = launch(src[0][idx].contiguous(), src[1][idx].contiguous(), pc)
-            big = torch.full((nq, pc, 12), float("nan"), dtype=torch.float64, device="cuda")
-            big[:, : int(point_cap)] = out["points"]
-            big[idx] = r["points"]
-            out["points"] = big
-            for k in ("n_points", "total_time", "status"):
-                out[k][idx] = r[k]
-    return out
+    return _traj3d_batch(torch, _xyz_arrays(paths) if cells is None else None, cells, 12, 3, wp_limit,
+                         max_waypoints, eval_t, point_cap, estimate, call, retry_overflow)[0]

@@ -19,6 +19,7 @@
 // 1e-10 relative and its yaw rate by more than the 1e-9 bound), and its `t ** k` is libm's pow,
 // correctly rounded: here a double-double product chain.
 #include "pmp_internal.h"
+#include "traj_entry.h"
 #include "traj_sample.h"
 
 namespace {
@@ -53,7 +54,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void po
     const int q = blockIdx.x;
     const int lane = lane_id();
     if (q >= nq) return;
-    const int n = cells ? path_len[q] : off[q + 1] - off[q];
+    int wp_cap;
+    const int n = traj_waypoint_count(q, off, cells, path_len, path_cap, nmax, wp_cap);
     // LDS: P [3][nmax] | V [3][nmax] | T [nmax] | S [nmax + 1] | stage [kCh][kRow] | tq [kCh] | meta
     double* P = sm;
     double* V = P + 3 * (size_t)nmax;
@@ -62,28 +64,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void po
     double* stage = S + nmax + 1;
     double* tq = stage + kCh * kRow;
     int* meta = (int*)(tq + kCh);
-    const int wp_cap = cells && path_cap < nmax ? path_cap : nmax;
     if (n < 2 || n > wp_cap) {  // n < 2: the reference raises ValueError (polynomial_trajectory.py:191)
-        if (lane == 0) {
-            st_out[q] = n < 2 ? PMP_REF_RAISES : PMP_CAP_OVERFLOW;
-            np_out[q] = 0;
-            total_out[q] = 0.0;
-        }
+        traj_refuse(lane, q, n < 2 ? PMP_REF_RAISES : PMP_CAP_OVERFLOW, st_out, np_out, total_out);
         return;
     }
-    for (int i = lane; i < n; i += 64) {
-        if (cells) {
-            const int v = cells[(size_t)q * path_cap + i];
-            P[i] = (double)(v / (Y * Z));
-            P[nmax + i] = (double)((v / Z) % Y);
-            P[2 * nmax + i] = (double)(v % Z);
-        } else {
-            const double* w = path + 3 * ((size_t)off[q] + i);
-            P[i] = w[0];
-            P[nmax + i] = w[1];
-            P[2 * nmax + i] = w[2];
-        }
-    }
+    traj_load_waypoints(P, nmax, n, q, lane, path, off, cells, path_cap, Y, Z);
     double b0[3] = {0, 0, 0}, b1[3] = {0, 0, 0}, b2[3] = {0, 0, 0}, b3[3] = {0, 0, 0};  // v0, v1, a0, a1
     if (bc)
         for (int d = 0; d < 3; d++) {
@@ -157,12 +142,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void po
     bool done = false;
     traj_prev pv;
     while (!done) {
-        if (lane == 0) traj_next_times(eval_t, n_eval, count, dt, total, t, last_t, tq, meta);
-        __syncthreads();
-        const int k = meta[0];
-        done = meta[1] != 0;
-        const int room = point_cap - count;            // rows of this round that fit the buffer
-        const int nrow = room < 0 ? 0 : (room < k ? room : k);
+        const traj_round r = traj_round_head(lane, eval_t, n_eval, count, dt, total, t, last_t, tq, meta, point_cap);
+        done = r.done;
+        const int nrow = r.nrow;
         double my_t = 0.0, vx = 0.0, vy = 0.0;
         double* o = stage + lane * kRow;
         if (lane < nrow) {
@@ -209,16 +191,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void po
             o[14] = rate_col;
         }
         __syncthreads();
-        for (int j = lane; j < nrow * kRow; j += 64) pts[(size_t)count * kRow + j] = stage[j];
-        count += k;
+        traj_store_rows<kRow>(pts, stage, count, nrow, lane);
+        count += r.k;
     }
     if (lane == 0) {
         np_out[q] = count;
         st_out[q] = count > point_cap ? PMP_PATH_OVERFLOW : PMP_FOUND;
     }
 }
-
-bool finite3(const double* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
 }  // namespace
 
@@ -231,28 +211,25 @@ extern "C" int pmp_polytraj3d_batch(pmp_ctx* ctx, void* stream, const pmp_polytr
                                     double* total_time, double* segment_times, int32_t* status, const double* eval_t,
                                     int n_eval, double sample_dt)
 {
+    const char* fn = "pmp_polytraj3d_batch";
     if (!ctx) return PMP_EINVAL;
-    if (!prm || nq < 0 || max_waypoints < 2 || point_cap < 1 || n_eval < 0 || (eval_t && n_eval < 1))
-        return pmp_set_err(ctx, PMP_EINVAL, "pmp_polytraj3d_batch: bad params/nq/max_waypoints/point_cap/n_eval");
+    if (!prm || nq < 0 || max_waypoints < 2)
+        return pmp_set_err(ctx, PMP_EINVAL, "pmp_polytraj3d_batch: bad params/nq/max_waypoints");
     if (max_waypoints > kMaxWp)
         return pmp_set_err(ctx, PMP_EINVAL, "pmp_polytraj3d_batch: max_waypoints too large for the LDS stage (<= 880)");
     // the reference divides by zero or never leaves its sampling loop on these
     const double amin = std::min(std::min(prm->max_acceleration[0], prm->max_acceleration[1]), prm->max_acceleration[2]);
     if (!finite3(prm->max_velocity) || !finite3(prm->max_acceleration) || !(amin > 0))
         return pmp_set_err(ctx, PMP_EINVAL, "pmp_polytraj3d_batch: constraints must be finite and min(max_acceleration) > 0");
-    if (!std::isfinite(prm->min_time_step) || !(prm->min_time_step > 0) || !std::isfinite(sample_dt) || sample_dt < 0)
-        return pmp_set_err(ctx, PMP_EINVAL, "pmp_polytraj3d_batch: min_time_step must be > 0 and sample_dt >= 0, finite");
+    if (int rc = traj_check_sampling(ctx, fn, point_cap, eval_t, n_eval, prm->min_time_step, sample_dt)) return rc;
     if (nq == 0) return PMP_OK;
-    const bool form_xyz = path_xyz && path_off, form_cells = cells && path_len;
-    if (form_xyz == form_cells)
-        return pmp_set_err(ctx, PMP_EINVAL, "pmp_polytraj3d_batch: give either path_xyz + path_off or cells + path_len");
-    if (form_cells && (path_cap < 1 || X < 1 || Y < 1 || Z < 1 || (int64_t)X * Y * Z > INT32_MAX))
-        return pmp_set_err(ctx, PMP_EINVAL, "pmp_polytraj3d_batch: bad path_cap or grid size");
+    bool form_cells;
+    if (int rc = traj_check_paths(ctx, fn, path_xyz, path_off, cells, path_len, path_cap, X, Y, Z, form_cells)) return rc;
     if (!points || !n_points || !total_time || !segment_times || !status)
         return pmp_set_err(ctx, PMP_EINVAL, "pmp_polytraj3d_batch: null pointer argument");
     PMP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipLaunchKernelGGL(polytraj3d_kernel, dim3(nq), dim3(64), 8 * lds_doubles(max_waypoints), (hipStream_t)stream, *prm,
-                       nq, form_xyz ? path_xyz : nullptr, form_xyz ? path_off : nullptr, form_cells ? cells : nullptr,
+                       nq, form_cells ? nullptr : path_xyz, form_cells ? nullptr : path_off, form_cells ? cells : nullptr,
                        form_cells ? path_len : nullptr, path_cap, Y, Z, bc, max_waypoints, point_cap, points, n_points,
                        total_time, segment_times, status, eval_t, n_eval, sample_dt);
     PMP_HIP_CHECK(ctx, hipGetLastError());

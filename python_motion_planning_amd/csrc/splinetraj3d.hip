@@ -27,6 +27,7 @@
 // of q'', q' and q on the same span, so one walk serves all three.  Plain IEEE doubles,
 // -ffp-contract=off.
 #include "pmp_internal.h"
+#include "traj_entry.h"
 #include "traj_sample.h"
 
 namespace {
@@ -142,17 +143,10 @@ __device__ __forceinline__ void bsp_eval(const Bsp& B, double x, double (&pos)[3
     bsp_stage<0, kPos, kD1, kD2>(B, x, bsp_span(B, x), h, pos, q1, q2, row);
 }
 
-// interp1d(xs, np.linspace(0, 1, ns), kind='linear', fill_value='extrapolate')(x) (scipy _call_linear:
-// searchsorted (left), clipped to [1, ns - 1]), then np.clip(., 0, 1)
+// interp1d(xs, np.linspace(0, 1, ns), kind='linear', fill_value='extrapolate')(x), then np.clip(., 0, 1)
 __device__ __forceinline__ double interp01(const double* xs, int ns, double x)
 {
-    int lo = 0, hi = ns;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (xs[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    const int h = lo < 1 ? 1 : (lo > ns - 1 ? ns - 1 : lo), l0 = h - 1;
+    const int h = traj_interp_upper(xs, ns, x), l0 = h - 1;
     const double xl = xs[l0], xh = xs[h], yl = lin01(ns, l0), yh = lin01(ns, h);
     const double u = (yh - yl) / (xh - xl) * (x - xl) + yl;
     return u < 0.0 ? 0.0 : (u > 1.0 ? 1.0 : u);
@@ -180,7 +174,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sp
     const int q = blockIdx.x;
     const int lane = lane_id();
     if (q >= nq) return;
-    const int n = cells ? path_len[q] : off[q + 1] - off[q];
+    int wp_cap;
+    const int n = traj_waypoint_count(q, off, cells, path_len, path_cap, nmax, wp_cap);
     double* C0 = sm;  // the waypoints, then the spline's coefficients
     double* C1 = C0 + 3 * (size_t)nmax;
     double* C2 = C1 + 3 * (size_t)nmax;
@@ -191,33 +186,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sp
     double* stage = tab + kNs + kNarc;
     double* tq = stage + kCh * kRow;
     int* meta = (int*)(tq + kCh);
-    const int wp_cap = cells && path_cap < nmax ? path_cap : nmax;
-    auto refuse = [&](int st) {
-        if (lane == 0) {
-            st_out[q] = st;
-            np_out[q] = 0;
-            total_out[q] = 0.0;
-        }
-    };
+    auto refuse = [&](int st) { traj_refuse(lane, q, st, st_out, np_out, total_out); };
     // n < 3: two waypoints give k = 1, whose derivative(2) raises (:120); k = 1 likewise
     const int k = C.spline_degree < n - 1 ? C.spline_degree : n - 1;
     if (n < 3 || k < 2 || n > wp_cap) {
         refuse(n > wp_cap ? PMP_CAP_OVERFLOW : PMP_REF_RAISES);
         return;
     }
-    for (int i = lane; i < n; i += 64) {
-        if (cells) {
-            const int v = cells[(size_t)q * path_cap + i];
-            C0[i] = (double)(v / (Y * Z));
-            C0[nmax + i] = (double)((v / Z) % Y);
-            C0[2 * nmax + i] = (double)(v % Z);
-        } else {
-            const double* w = path + 3 * ((size_t)off[q] + i);
-            C0[i] = w[0];
-            C0[nmax + i] = w[1];
-            C0[2 * nmax + i] = w[2];
-        }
-    }
+    traj_load_waypoints(C0, nmax, n, q, lane, path, off, cells, path_cap, Y, Z);
     __syncthreads();
     // _compute_centripetal_parameterization (:60-77) and get_path_length (trajectory_base.py:144-149)
     for (int i = lane + 1; i < n; i += 64) {
@@ -405,18 +381,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sp
         traj_prev pv;
         count = 0;
         while (!done) {
-            if (lane == 0) {
-                bool app;
-                traj_next_times(et, n_eval, count, dt, bound, t, last_t, tq, meta, &app);
-                meta[2] = app ? 1 : 0;
-            }
-            __syncthreads();
-            const int kk = meta[0];
-            done = meta[1] != 0;
+            const traj_round r = traj_round_head(lane, et, n_eval, count, dt, bound, t, last_t, tq, meta, point_cap);
+            const int kk = r.k;
+            done = r.done;
             // the final point of generate() (:250-263) and of the constant-speed loop (:382-392): u = 1, at rest
-            const bool app = (gen || mode == kConstSpeed) && meta[2] != 0 && lane == kk - 1;
-            const int room = point_cap - count;
-            const int nrow = pass == 0 ? kk : (room < 0 ? 0 : (room < kk ? room : kk));
+            const bool app = (gen || mode == kConstSpeed) && r.appended && lane == kk - 1;
+            const int nrow = pass == 0 ? kk : r.nrow;  // the first pass stores nothing: it sees every point
             double my_t = 0.0, vx = 0.0, vy = 0.0;
             double* o = stage + lane * kRow;
             if (lane < nrow) {
@@ -480,7 +450,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sp
                     o[11] = rate_col;
                 }
                 __syncthreads();
-                for (int j = lane; j < nrow * kRow; j += 64) pts[(size_t)count * kRow + j] = stage[j];
+                traj_store_rows<kRow>(pts, stage, count, nrow, lane);
             }
             count += kk;
             __syncthreads();
@@ -510,8 +480,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sp
     }
 }
 
-bool finite3(const double* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
-
 }  // namespace
 
 extern "C" int pmp_splinetraj3d_max_waypoints(void) { return kMaxWp; }
@@ -523,9 +491,10 @@ extern "C" int pmp_splinetraj3d_batch(pmp_ctx* ctx, void* stream, const pmp_spli
                                       int32_t* status, const double* eval_t, int n_eval, double sample_dt,
                                       int constant_speed)
 {
+    const char* fn = "pmp_splinetraj3d_batch";
     if (!ctx) return PMP_EINVAL;
-    if (!prm || nq < 0 || max_waypoints < 3 || point_cap < 1 || n_eval < 0 || (eval_t && n_eval < 1))
-        return pmp_set_err(ctx, PMP_EINVAL, "pmp_splinetraj3d_batch: bad params/nq/max_waypoints/point_cap/n_eval");
+    if (!prm || nq < 0 || max_waypoints < 3)
+        return pmp_set_err(ctx, PMP_EINVAL, "pmp_splinetraj3d_batch: bad params/nq/max_waypoints");
     if (max_waypoints > kMaxWp)
         return pmp_set_err(ctx, PMP_EINVAL, "pmp_splinetraj3d_batch: max_waypoints too large for the LDS block (<= 500)");
     if (prm->spline_degree < 1 || prm->spline_degree > 5)  // scipy: k should be 1 <= k <= 5
@@ -537,21 +506,17 @@ extern "C" int pmp_splinetraj3d_batch(pmp_ctx* ctx, void* stream, const pmp_spli
     if (!finite3(prm->max_velocity) || !finite3(prm->max_acceleration) || !(vmin > 0) || !(amin > 0))
         return pmp_set_err(ctx, PMP_EINVAL,
                            "pmp_splinetraj3d_batch: constraints must be finite, min|max_velocity| > 0, min(max_acceleration) > 0");
-    if (!std::isfinite(prm->min_time_step) || !(prm->min_time_step > 0) || !std::isfinite(sample_dt) || sample_dt < 0)
-        return pmp_set_err(ctx, PMP_EINVAL, "pmp_splinetraj3d_batch: min_time_step must be > 0 and sample_dt >= 0, finite");
+    if (int rc = traj_check_sampling(ctx, fn, point_cap, eval_t, n_eval, prm->min_time_step, sample_dt)) return rc;
     if ((eval_t != nullptr) + (sample_dt > 0) + (constant_speed != 0) > 1)
         return pmp_set_err(ctx, PMP_EINVAL, "pmp_splinetraj3d_batch: eval_t, sample_dt and constant_speed exclude each other");
     if (nq == 0) return PMP_OK;
-    const bool form_xyz = path_xyz && path_off, form_cells = cells && path_len;
-    if (form_xyz == form_cells)
-        return pmp_set_err(ctx, PMP_EINVAL, "pmp_splinetraj3d_batch: give either path_xyz + path_off or cells + path_len");
-    if (form_cells && (path_cap < 1 || X < 1 || Y < 1 || Z < 1 || (int64_t)X * Y * Z > INT32_MAX))
-        return pmp_set_err(ctx, PMP_EINVAL, "pmp_splinetraj3d_batch: bad path_cap or grid size");
+    bool form_cells;
+    if (int rc = traj_check_paths(ctx, fn, path_xyz, path_off, cells, path_len, path_cap, X, Y, Z, form_cells)) return rc;
     if (!points || !n_points || !total_time || !status)
         return pmp_set_err(ctx, PMP_EINVAL, "pmp_splinetraj3d_batch: null pointer argument");
     PMP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipLaunchKernelGGL(splinetraj3d_kernel, dim3(nq), dim3(64), 8 * lds_doubles(max_waypoints), (hipStream_t)stream, *prm,
-                       nq, form_xyz ? path_xyz : nullptr, form_xyz ? path_off : nullptr, form_cells ? cells : nullptr,
+                       nq, form_cells ? nullptr : path_xyz, form_cells ? nullptr : path_off, form_cells ? cells : nullptr,
                        form_cells ? path_len : nullptr, path_cap, Y, Z, max_waypoints, point_cap, points, n_points,
                        total_time, status, eval_t, n_eval, sample_dt, constant_speed);
     PMP_HIP_CHECK(ctx, hipGetLastError());

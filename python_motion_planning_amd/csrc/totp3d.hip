@@ -436,26 +436,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void to
     bool done = false;
     traj_prev pv;  // the previous point (wave-uniform)
     while (!done) {
-        if (lane == 0) traj_next_times(eval_t, n_eval, count, T.min_time_step, total, t, last_t, tq, meta);
-        __syncthreads();
-        const int k = meta[0];
-        done = meta[1] != 0;
+        const traj_round r = traj_round_head(lane, eval_t, n_eval, count, T.min_time_step, total, t, last_t, tq, meta, point_cap);
+        const int k = r.k;
+        done = r.done;
         double my_t = 0.0;
         double o[12];
         o[4] = 0.0;
         o[5] = 0.0;
         if (lane < k) {
             const double tc = tq[lane] < 0.0 ? 0.0 : (tq[lane] > total ? total : tq[lane]);
-            // interp1d(kind='linear', fill_value='extrapolate') (scipy _call_linear): searchsorted
-            // (left), clipped to [1, ns - 1]
-            int lo = 0, hi = ns;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (tp[mid] < tc) lo = mid + 1;
-                else hi = mid;
-            }
-            int h = lo < 1 ? 1 : (lo > ns - 1 ? ns - 1 : lo);
-            const int l0 = h - 1;
+            // interp1d(kind='linear', fill_value='extrapolate') of s, s_dot and s_ddot on the time profile
+            const int h = traj_interp_upper(tp, ns, tc), l0 = h - 1;
             const double xl = tp[l0], xh = tp[h], dxl = tc - xl;
             const double s = (lin(L, ns, h) - lin(L, ns, l0)) / (xh - xl) * dxl + lin(L, ns, l0);
             const double sdt = (sd[h] - sd[l0]) / (xh - xl) * dxl + sd[l0];
@@ -473,11 +464,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void to
         }
         // yaw, and the yaw rate from the previous point (traj_sample.h)
         traj_yaw_tail(lane, k, !eval_t, o[4], o[5], my_t, pv, o[10], o[11]);
-        if (lane < k) {
-            const int idx = count + lane;
-            if (idx < point_cap)
-                for (int j = 0; j < 12; j++) pts[(size_t)idx * 12 + j] = o[j];
-        }
+        if (lane < r.nrow)  // the rows that fit the buffer, one per lane
+            for (int j = 0; j < 12; j++) pts[(size_t)(count + lane) * 12 + j] = o[j];
         count += k;
         __syncthreads();
     }

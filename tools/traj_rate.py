@@ -1,26 +1,29 @@
 #!/usr/bin/env python3
-"""Trajectories/s and points/s of SplineTrajectory3D (splinetraj3d.hip) on C5 paths planned by the 3D A*
-kernel, with PolynomialTrajectory3D (polytraj3d.hip) and TimeOptimalTrajectory3D (totp3d.hip) on the same
-paths timed in the same run for scale.
+"""Trajectories/s, points/s and store bandwidth of PolynomialTrajectory3D (polytraj3d.hip) or
+SplineTrajectory3D (splinetraj3d.hip) on C5 paths planned by the 3D A* kernel, with the other generators on
+the same paths timed in the same run for scale.
 
-    python tools/splinetraj3d_rate.py [--paths 4096] [--warmup 3] [--repeats 9] [--out FILE]
-                                      [--reference-src DIR [--reference-paths 6]]
+    python tools/traj_rate.py --kind polynomial|spline [--paths 4096] [--warmup 3] [--repeats 9] [--out FILE]
+                              [--reference-src DIR [--reference-paths 6]]
 
 Workload: `--paths` C5 queries (workloads.c5_workload) planned by batch.astar3d_batch, the constraints of
-examples/3d_example.py:104-109 (2 / 2 / 1.5 m/s, 1.5 / 1.5 / 1 m/s^2, dt 0.05), spline_degree = 3 as the
-example passes it.  Per repeat, between two device events each:
-  kernel_cells / kernel_host   pmp_splinetraj3d_batch alone on buffers allocated once: the paths as the
+examples/3d_example.py:104-109 (2 / 2 / 1.5 m/s, 1.5 / 1.5 / 1 m/s^2, dt 0.05), for the spline
+spline_degree = 3 as the example passes it.  Per repeat, between two device events each:
+  kernel_cells / kernel_host   the kind's C entry alone on buffers allocated once: the paths as the
                                planner's cell ids on the device / as uploaded f64 waypoints
-  call_cells                   batch.splinetraj3d_batch as a caller uses it, from the planner's device
-                               tensors (sizing, launch, the status read of the overflow retry)
-  polytraj / totp              batch.polytraj3d_batch (cells form) / batch.totp3d_batch (host-decoded
-                               paths) on the same paths
+  call_cells                   the kind's batch call as a caller uses it, from the planner's device tensors
+                               (sizing, launch, the status read of the overflow retry)
+  call_host   (polynomial)     the same from the paths copied to the host and decoded there (that copy
+                               included)
+  polytraj    (spline)         batch.polytraj3d_batch (cells form) on the same paths
+  totp                         batch.totp3d_batch on the host-decoded paths
 The legs alternate inside each repeat, so drift on a shared machine falls on all of them alike.
 Reported per leg: the median over the repeats and its min-max spread; for the kernel legs also the
-bytes of point rows stored (96 B per point) per second as a fraction of the 8 TB/s HBM peak.
+bytes of point rows stored (120 B per point, 96 B for the spline) per second as a fraction of the 8 TB/s
+HBM peak.
 With --reference-src (the reference's `src` directory, where it is installed) the reference's own
-SplineTrajectory3D.generate() is timed on one CPU core on the first `--reference-paths` paths;
-with no HIP device only that part runs (on seeded random-walk paths).
+generate() of the kind is timed on one CPU core on the first `--reference-paths` paths; with no HIP device
+only that part runs (on seeded random-walk paths).
 One JSON line per leg."""
 import argparse
 import ctypes
@@ -37,7 +40,7 @@ VMAX, AMAX, DT, DEGREE = (2.0, 2.0, 1.5), (1.5, 1.5, 1.0), 0.05, 3
 HBM_PEAK = 8.0e12
 
 
-def reference_seconds(src, paths):
+def reference_seconds(src, paths, spline):
     import types
     import unittest.mock
 
@@ -45,12 +48,13 @@ def reference_seconds(src, paths):
     sys.modules.setdefault("osqp", types.ModuleType("osqp"))
     sys.modules["pyvista"] = unittest.mock.MagicMock()
     os.environ.setdefault("MPLBACKEND", "Agg")
-    from python_motion_planning.trajectory import SplineTrajectory3D, TrajectoryConstraints
+    from python_motion_planning import trajectory as T
 
-    cons = TrajectoryConstraints(np.array(VMAX), np.array(AMAX), np.array([1.0, 1.0, 0.8]), DT)
+    cons = T.TrajectoryConstraints(np.array(VMAX), np.array(AMAX), np.array([1.0, 1.0, 0.8]), DT)
     secs, npts = [], []
     for p in paths:
-        tr = SplineTrajectory3D([tuple(v) for v in p], cons, spline_degree=DEGREE)
+        wp = [tuple(v) for v in p]
+        tr = T.SplineTrajectory3D(wp, cons, spline_degree=DEGREE) if spline else T.PolynomialTrajectory3D(wp, cons)
         t0 = time.perf_counter()
         pts = tr.generate()
         secs.append(time.perf_counter() - t0)
@@ -62,6 +66,7 @@ def reference_seconds(src, paths):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--kind", choices=("polynomial", "spline"), required=True)
     ap.add_argument("--paths", type=int, default=4096)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=9)
@@ -69,6 +74,7 @@ def main():
     ap.add_argument("--reference-paths", type=int, default=6)
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
+    spline = a.kind == "spline"
 
     import torch
 
@@ -85,9 +91,10 @@ def main():
         walks = []
         for n in (18, 22, 26, 30, 34, 60):
             st = rng.integers(-1, 2, size=(n, 3))
-            st[:, 0] = 1  # no repeated waypoint
+            if spline:
+                st[:, 0] = 1  # no repeated waypoint
             walks.append(np.cumsum(st, axis=0) + 30)
-        emit(reference_seconds(a.reference_src, walks[: a.reference_paths]))
+        emit(reference_seconds(a.reference_src, walks[: a.reference_paths], spline))
     else:
         from python_motion_planning_amd import _lib, batch, workloads as wl
 
@@ -96,41 +103,57 @@ def main():
         pa = batch.astar3d_batch(occ, s, g, path_cap=256)
         pl = pa["path_len"].cpu().numpy()
         nq = len(pl)
-        P = pa["path"].cpu().numpy()
-        paths = []
-        for q in range(nq):
-            v = P[q, : pl[q]].astype(np.int64)
-            paths.append(np.stack([v // (Y * Z), (v // Z) % Y, v % Z], axis=1).astype(np.float64))
-        prm = _lib.SplineTrajParams.make(VMAX, AMAX, DT, DEGREE)
+
+        def host_paths():
+            P = pa["path"].cpu().numpy()
+            out = []
+            for q in range(nq):
+                v = P[q, : pl[q]].astype(np.int64)
+                out.append(np.stack([v // (Y * Z), (v // Z) % Y, v % Z], axis=1).astype(np.float64))
+            return out
+
+        paths = host_paths()
         pprm = _lib.PolyTrajParams.make(VMAX, AMAX, DT)
         tprm = _lib.TotpParams.make(VMAX, AMAX, DT, 0.05)
+        prm = _lib.SplineTrajParams.make(VMAX, AMAX, DT, DEGREE) if spline else pprm
+        call = batch.splinetraj3d_batch if spline else batch.polytraj3d_batch
+        row_bytes = 96 if spline else 120
         L, ctx = _lib.load_library(), _lib.context()
         cells = (pa["path"], pa["path_len"], (X, Y, Z))
-        first = batch.splinetraj3d_batch(None, prm, cells=cells)
+        first = call(None, prm, cells=cells)
         assert int((first["status"] == 2).sum()) == 0
         npts = int(first["n_points"].sum())
         ntraj = int((first["status"] == 0).sum())
         pc = int(first["points"].shape[1])
-        nmax = int(max(3, pl.max()))
+        nmax = int(max(3 if spline else 2, pl.max()))
         flat = torch.as_tensor(np.concatenate(paths), device="cuda")
         off = np.zeros(nq + 1, np.int32)
         off[1:] = np.cumsum(pl)
         off_d = torch.as_tensor(off, device="cuda")
         o = dict(points=first["points"], n=torch.empty(nq, dtype=torch.int32, device="cuda"),
-                 tt=torch.empty(nq, dtype=torch.float64, device="cuda"), st=torch.empty(nq, dtype=torch.int32, device="cuda"))
+                 tt=torch.empty(nq, dtype=torch.float64, device="cuda"),
+                 seg=torch.empty((nq, 256), dtype=torch.float64, device="cuda"),
+                 st=torch.empty(nq, dtype=torch.int32, device="cuda"))
 
         def kernel(as_cells):
             src = (None, None, pa["path"].data_ptr(), pa["path_len"].data_ptr(), 256, X, Y, Z) if as_cells else \
                   (flat.data_ptr(), off_d.data_ptr(), None, None, 0, 0, 0, 0)
-            rc = L.pmp_splinetraj3d_batch(ctx, _lib.stream_ptr(), ctypes.byref(prm), nq, *src, nmax, pc,
-                                          o["points"].data_ptr(), o["n"].data_ptr(), o["tt"].data_ptr(), o["st"].data_ptr(),
-                                          None, 0, 0.0, 0)
-            _lib.check(ctx, rc, "pmp_splinetraj3d_batch")
+            head = (ctx, _lib.stream_ptr(), ctypes.byref(prm), nq) + src
+            outs = (o["points"].data_ptr(), o["n"].data_ptr(), o["tt"].data_ptr())
+            if spline:
+                rc = L.pmp_splinetraj3d_batch(*head, nmax, pc, *outs, o["st"].data_ptr(), None, 0, 0.0, 0)
+            else:
+                rc = L.pmp_polytraj3d_batch(*head, None, nmax, pc, *outs, o["seg"].data_ptr(), o["st"].data_ptr(),
+                                            None, 0, 0.0)
+            _lib.check(ctx, rc, "pmp_splinetraj3d_batch" if spline else "pmp_polytraj3d_batch")
 
         legs = dict(kernel_cells=lambda: kernel(True), kernel_host=lambda: kernel(False),
-                    call_cells=lambda: batch.splinetraj3d_batch(None, prm, cells=cells, max_waypoints=nmax),
-                    polytraj=lambda: batch.polytraj3d_batch(None, pprm, cells=cells, max_waypoints=nmax),
-                    totp=lambda: batch.totp3d_batch(paths, tprm))
+                    call_cells=lambda: call(None, prm, cells=cells, max_waypoints=nmax))
+        if spline:
+            legs["polytraj"] = lambda: batch.polytraj3d_batch(None, pprm, cells=cells, max_waypoints=nmax)
+        else:
+            legs["call_host"] = lambda: batch.polytraj3d_batch(host_paths(), prm)
+        legs["totp"] = lambda: batch.totp3d_batch(paths, tprm)
         secs = {k: [] for k in legs}
         for rep in range(a.warmup + a.repeats):
             for k, fn in legs.items():
@@ -144,21 +167,24 @@ def main():
                 if rep >= a.warmup:
                     secs[k].append(e0.elapsed_time(e1) * 1e-3)
         assert int(o["n"].sum()) == npts and int((o["st"] == 0).sum()) == ntraj
-        other = dict(polytraj=int(batch.polytraj3d_batch(None, pprm, cells=cells, max_waypoints=nmax)["n_points"].sum()),
-                     totp=int(batch.totp3d_batch(paths, tprm)["n_points"].sum()))
+        other = {k: int(legs[k]()["n_points"].sum()) for k in ("polytraj", "totp") if k in legs}
         for k in legs:
             v = np.array(secs[k])
             n_p = other.get(k, npts)
-            d = dict(leg=k, paths=nq, trajectories=ntraj, points=n_p, waypoints_max=nmax, repeats=a.repeats,
-                     median_ms=float(np.median(v) * 1e3), min_ms=float(v.min() * 1e3), max_ms=float(v.max() * 1e3),
-                     trajectories_per_s=float(ntraj / np.median(v)), points_per_s=float(n_p / np.median(v)))
+            d = dict(leg=k, paths=nq, trajectories=ntraj, points=n_p)
+            if spline:
+                d["waypoints_max"] = nmax
+            d.update(repeats=a.repeats, median_ms=float(np.median(v) * 1e3), min_ms=float(v.min() * 1e3),
+                     max_ms=float(v.max() * 1e3), trajectories_per_s=float(ntraj / np.median(v)),
+                     points_per_s=float(n_p / np.median(v)))
             if k.startswith("kernel"):
-                d["store_bytes"] = npts * 96
-                d["store_GBps"] = float(npts * 96 / np.median(v) * 1e-9)
-                d["hbm_peak_frac"] = float(npts * 96 / np.median(v) / HBM_PEAK)
+                d["store_bytes"] = npts * row_bytes
+                d["store_GBps"] = float(npts * row_bytes / np.median(v) * 1e-9)
+                d["hbm_peak_frac"] = float(npts * row_bytes / np.median(v) / HBM_PEAK)
             emit(d)
         if a.reference_src:
-            emit(reference_seconds(a.reference_src, [p for p in paths if len(p) >= 3][: a.reference_paths]))
+            usable = [p for p in paths if len(p) >= 3] if spline else paths
+            emit(reference_seconds(a.reference_src, usable[: a.reference_paths], spline))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "a") as f:
