@@ -2,6 +2,13 @@
 
 These are the calls the drop-in planner classes, the bench and the parity tests go through;
 each one launches the gfx950 kernels of libpmp_hip.so asynchronously on the current stream.
+
+The grid-search and sampling wrappers are each: intake, allocate, one C call, _lib.check, extras, return.
+What they share is here once: _open (torch, library, context), _occ2d / _occ3d_bits (occupancy intake),
+_endpoints (start / goal upload), _records (the cost / path_len / path / count / status block and its
+optional blocks), _manhattan and _path_cap; the sampling trio has _sample_inputs and _tree_outputs.  The C
+call stays written out in each wrapper: its argument order is the ABI.  query0 is the read-back of the
+drop-in classes.
 """
 from __future__ import annotations
 
@@ -27,6 +34,86 @@ def occ_bits_device(occ, torch=None):
     return torch.as_tensor(words.view(np.int32), device="cuda")
 
 
+def _open():
+    """(torch, the loaded library, the context): raises PMPError without a HIP device."""
+    return _lib.device_check(), _lib.load_library(), _lib.context()
+
+
+def _occ2d(torch, occ, occ_bits=None):
+    """(occ_bits, W, H) of a 2D occupancy: a uint8 [W, H] array (x-major), a Grid, or, with occ_bits
+    given (device words, used as they are), anything with the shape: (W, H) itself or the array."""
+    if occ_bits is not None:
+        W, H = (occ if isinstance(occ, tuple) else occ.shape)[:2]
+    elif hasattr(occ, "occupancy_words"):  # a Grid
+        W, H = occ.x_range, occ.y_range
+        occ_bits = torch.as_tensor(occ.occupancy_words().view(np.int32), device="cuda")
+    else:
+        occ = np.asarray(occ)
+        W, H = occ.shape[:2]
+        occ_bits = occ_bits_device(occ, torch)
+    return occ_bits, int(W), int(H)
+
+
+def _occ3d_bits(torch, occ, occ_bits=None):
+    """(device words, per_query, (X, Y, Z)) of a shared [X, Y, Z] or per-query [nq, X, Y, Z] grid; with
+    occ_bits given, `occ` only supplies the shape."""
+    shape = tuple(occ) if isinstance(occ, tuple) else np.asarray(occ).shape
+    per_query = len(shape) == 4
+    if occ_bits is None:
+        occ = np.asarray(occ)
+        words = np.stack([pack_bits(o) for o in occ]) if per_query else pack_bits(occ)
+        occ_bits = torch.as_tensor(np.ascontiguousarray(words).view(np.int32), device="cuda")
+    return occ_bits, per_query, tuple(int(d) for d in shape[-3:])
+
+
+def _endpoints(torch, starts, goals, d, dtype):
+    """(s, g, nq): starts and goals as [nq, d] device tensors of dtype."""
+    s = _dev(torch, starts, dtype).reshape(-1, d)
+    return s, _dev(torch, goals, dtype).reshape(-1, d), int(s.shape[0])
+
+
+def _manhattan(heuristic: str) -> int:
+    """The C entries' heuristic flag: 1 = manhattan, 0 = euclidean."""
+    return 1 if heuristic == "manhattan" else 0
+
+
+def _path_cap(path_cap, cells, bound=1 << 16):
+    """The caller's path_cap, else room for every cell once, up to bound (None: unbounded)."""
+    if path_cap is not None:
+        return int(path_cap)
+    return cells + 1 if bound is None else min(cells + 1, bound)
+
+
+# the per-query blocks a wrapper may attach: dtype and width (None: the capacity the wrapper gives)
+_OPTIONAL = dict(expand=("int32", None), expand_parent=("int32", None), expand_g=("float64", None),
+                 counters=("int64", 4))
+
+
+def _records(torch, lead, path_cap, count="n_expanded", count_dtype="int32", path_lead=None, **optional):
+    """The record block of a grid planner: cost f64, status i32 and the count column of shape lead ((nq,),
+    or (nq, R) with a record per round), path_len i32 and path i32 [.., path_cap] of shape path_lead (lead
+    unless given).  optional: name=capacity (counters=flag) for each per-query block the wrapper has
+    (_OPTIONAL), [nq, capacity] or None when that is 0 / False.  Nothing is initialised: the kernels write
+    every record.  Sizes go to torch.empty as separate integers: that overload parses faster than a tuple,
+    and on a small batch these allocations are most of the wrapper's host time."""
+    path_lead = lead if path_lead is None else path_lead
+    out = dict(cost=torch.empty(*lead, dtype=torch.float64, device="cuda"),
+               path_len=torch.empty(*path_lead, dtype=torch.int32, device="cuda"),
+               path=torch.empty(*path_lead, path_cap, dtype=torch.int32, device="cuda"),
+               status=torch.empty(*lead, dtype=torch.int32, device="cuda"))
+    out[count] = torch.empty(*lead, dtype=getattr(torch, count_dtype), device="cuda")
+    for k, cap in optional.items():
+        dtype, width = _OPTIONAL[k]
+        out[k] = torch.empty(lead[0], width or cap, dtype=getattr(torch, dtype), device="cuda") if cap else None
+    return out
+
+
+def query0(r, key, n, k=None):
+    """The first n entries of query 0's `key` (of its round or tree k, where it has them) in a result dict,
+    as numpy: what the drop-in classes read back."""
+    return r[key][((0,) if k is None else (0, k)) + (slice(n),)].cpu().numpy()
+
+
 def astar2d_batch(occ, starts, goals, heuristic: str = "euclidean", path_cap: int | None = None,
                   expand_cap: int = 0, counters: bool = False, occ_bits=None, reserve_slots: int | None = None,
                   heap_cap: int = 0, retry_overflow: bool = True, algo: str = "astar"):
@@ -42,32 +129,15 @@ def astar2d_batch(occ, starts, goals, heuristic: str = "euclidean", path_cap: in
     retry_overflow those queries are planned again on the GPU with the full bound (8 W H + 8
     entries) on fewer workers -- one host sync to read the statuses.
     """
-    torch = _lib.device_check()
-    L = _lib.load_library()
-    ctx = _lib.context()
-    if occ_bits is None:
-        W, H = int(occ.shape[0]), int(occ.shape[1])
-        occ_bits = occ_bits_device(occ, torch)
-    else:
-        W, H = (int(occ[0]), int(occ[1])) if isinstance(occ, tuple) else (int(occ.shape[0]), int(occ.shape[1]))
-    s = _dev(torch, starts, torch.int32).reshape(-1, 2)
-    g = _dev(torch, goals, torch.int32).reshape(-1, 2)
-    nq = int(s.shape[0])
-    if path_cap is None:
-        path_cap = min(W * H + 1, 1 << 16)
-    out = dict(
-        cost=torch.empty(nq, dtype=torch.float64, device="cuda"),
-        path_len=torch.empty(nq, dtype=torch.int32, device="cuda"),
-        path=torch.empty((nq, path_cap), dtype=torch.int32, device="cuda"),
-        n_expanded=torch.empty(nq, dtype=torch.int32, device="cuda"),
-        status=torch.empty(nq, dtype=torch.int32, device="cuda"),
-    )
-    out["expand"] = torch.empty((nq, expand_cap), dtype=torch.int32, device="cuda") if expand_cap else None
-    out["counters"] = torch.empty((nq, 4), dtype=torch.int64, device="cuda") if counters else None
+    torch, L, ctx = _open()
+    occ_bits, W, H = _occ2d(torch, occ, occ_bits)
+    s, g, nq = _endpoints(torch, starts, goals, 2, torch.int32)
+    path_cap = _path_cap(path_cap, W * H)
+    out = _records(torch, (nq,), path_cap, expand=expand_cap, counters=counters)
     if reserve_slots:
         _lib.check(ctx, L.pmp_astar2d_reserve(ctx, W, H, int(reserve_slots), int(heap_cap)), "pmp_astar2d_reserve")
     rc = L.pmp_graph2d_batch(ctx, _lib.stream_ptr(), _lib.ALGOS[algo], occ_bits.data_ptr(), W, H,
-                             1 if heuristic == "manhattan" else 0, s.data_ptr(), g.data_ptr(), nq,
+                             _manhattan(heuristic), s.data_ptr(), g.data_ptr(), nq,
                              out["cost"].data_ptr(), out["path_len"].data_ptr(), out["path"].data_ptr(), path_cap,
                              out["n_expanded"].data_ptr(), _lib.ptr(out["expand"]), int(expand_cap),
                              _lib.ptr(out["counters"]), out["status"].data_ptr())
@@ -90,7 +160,7 @@ def astar2d_full_bound(occ, starts, goals, heuristic="euclidean", path_cap=None,
     which no search exceeds) on at most 256 workers, then the context's geometry restored as it was --
     the host's own reservation (its explicit heap_cap, or the default when it asked for none, so the
     engine choice of later batches is unchanged) or launch-sized scratch."""
-    W, H = (int(occ[0]), int(occ[1])) if isinstance(occ, tuple) else (int(occ.shape[0]), int(occ.shape[1]))
+    W, H = (int(v) for v in (occ if isinstance(occ, tuple) else occ.shape)[:2])
     L, ctx = _lib.load_library(), _lib.context()
     nq = int(starts.shape[0])
     geo = np.zeros(6, np.int32)  # the geometry in force, restored after the re-run
@@ -132,7 +202,7 @@ class SingleQuery:
         self.sg_dev.copy_(self.sg_host, non_blocking=True)
         d, pc = self.dev.data_ptr(), self.path_cap
         rc = L.pmp_graph2d_batch(ctx, _lib.stream_ptr(), _lib.ALGOS[algo], occ_bits.data_ptr(), W, H,
-                                 1 if heuristic == "manhattan" else 0, self.sg_dev.data_ptr(),
+                                 _manhattan(heuristic), self.sg_dev.data_ptr(),
                                  self.sg_dev.data_ptr() + 8, 1, self.cost.data_ptr(), d + 8, d + 16, pc, d + 4,
                                  d + 16 + 4 * pc, self.expand_cap, None, d)
         _lib.check(ctx, rc, "pmp_graph2d_batch")
@@ -171,12 +241,10 @@ def astar2d_sharded(occ, starts, goals, dist=None, path_cap: int | None = None, 
     from . import shard
 
     torch = _lib.device_check()
-    occ_np = np.asarray(occ)
-    occ_bits = occ_bits_device(occ_np, torch)
-    shape = (int(occ_np.shape[0]), int(occ_np.shape[1]))
+    occ_bits, W, H = _occ2d(torch, occ)
 
     def plan(s, g):
-        r = astar2d_batch(shape, s, g, path_cap=path_cap, occ_bits=occ_bits, algo=algo, **kw)
+        r = astar2d_batch((W, H), s, g, path_cap=path_cap, occ_bits=occ_bits, algo=algo, **kw)
         return {k: r[k] for k in _RECORDS}
 
     return shard.run_sharded(dist, plan, np.asarray(starts), np.asarray(goals), device="cuda")
@@ -386,21 +454,11 @@ def dstar2d_batch(occ, starts, goals, path_cap: int | None = None, max_process: 
     """Batched DStar.plan (d_star.py:75-156) on one Grid.  occ uint8 [W, H] (x-major).
     Returns dict of device tensors: cost, path_len, path [nq, path_cap] (cells x*H+y, start -> goal),
     n_process (processState calls), status (4 = the reference raises: start unreachable)."""
-    torch = _lib.device_check()
-    L = _lib.load_library()
-    ctx = _lib.context()
-    occ = np.asarray(occ)
-    W, H = occ.shape
-    occ_bits = occ_bits_device(occ, torch)
-    s = _dev(torch, starts, torch.int32).reshape(-1, 2)
-    g = _dev(torch, goals, torch.int32).reshape(-1, 2)
-    nq = int(s.shape[0])
-    path_cap = W * H + 1 if path_cap is None else int(path_cap)
-    out = dict(cost=torch.empty(nq, dtype=torch.float64, device="cuda"),
-               path_len=torch.empty(nq, dtype=torch.int32, device="cuda"),
-               path=torch.empty((nq, path_cap), dtype=torch.int32, device="cuda"),
-               n_process=torch.empty(nq, dtype=torch.int64, device="cuda"),
-               status=torch.empty(nq, dtype=torch.int32, device="cuda"))
+    torch, L, ctx = _open()
+    occ_bits, W, H = _occ2d(torch, occ)
+    s, g, nq = _endpoints(torch, starts, goals, 2, torch.int32)
+    path_cap = _path_cap(path_cap, W * H, None)
+    out = _records(torch, (nq,), path_cap, "n_process", "int64")
     rc = L.pmp_dstar2d_batch(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), W, H,
                              s.data_ptr(), g.data_ptr(), nq, out["cost"].data_ptr(), out["path_len"].data_ptr(),
                              out["path"].data_ptr(), path_cap, out["n_process"].data_ptr(), out["status"].data_ptr(),
@@ -415,24 +473,15 @@ def dstar2d_onpress_batch(occ, starts, goals, presses, path_cap: int | None = No
     Returns dict of device tensors, per call r (0 = plan): cost [nq, R], path_len [nq, R],
     path [nq, R, path_cap] (cells x*H+y; plan start -> goal, presses the walk without the goal),
     n_process [nq, R] (len(EXPAND)), status [nq, R] (include/pmp.h)."""
-    torch = _lib.device_check()
-    L = _lib.load_library()
-    ctx = _lib.context()
-    occ = np.asarray(occ)
-    W, H = occ.shape
-    occ_bits = occ_bits_device(occ, torch)
-    s = _dev(torch, starts, torch.int32).reshape(-1, 2)
-    g = _dev(torch, goals, torch.int32).reshape(-1, 2)
-    nq = int(s.shape[0])
+    torch, L, ctx = _open()
+    occ_bits, W, H = _occ2d(torch, occ)
+    s, g, nq = _endpoints(torch, starts, goals, 2, torch.int32)
     pr = _dev(torch, presses, torch.int32)
     if pr.dim() != 3 or pr.shape[0] != nq or pr.shape[2] != 2:
         raise ValueError("presses must be [nq, npress, 2]")
     R = int(pr.shape[1]) + 1
-    path_cap = 4 * W * H + 8 if path_cap is None else int(path_cap)
-    i32 = dict(dtype=torch.int32, device="cuda")
-    out = dict(cost=torch.empty((nq, R), dtype=torch.float64, device="cuda"), path_len=torch.empty((nq, R), **i32),
-               path=torch.empty((nq, R, path_cap), **i32),
-               n_process=torch.empty((nq, R), dtype=torch.int64, device="cuda"), status=torch.empty((nq, R), **i32))
+    path_cap = 4 * W * H + 8 if path_cap is None else int(path_cap)  # a walk can visit a cell more than once
+    out = _records(torch, (nq, R), path_cap, "n_process", "int64")
     rc = L.pmp_dstar2d_onpress_batch(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), W, H, s.data_ptr(), g.data_ptr(), nq,
                                      pr.data_ptr(), R - 1, out["cost"].data_ptr(), out["path_len"].data_ptr(),
                                      out["path"].data_ptr(), path_cap, out["n_process"].data_ptr(),
@@ -448,27 +497,15 @@ def lpastar2d_batch(occ, starts, goals, heuristic: str = "euclidean", path_cap: 
     occ uint8 [W, H] (x-major).  Returns dict of device tensors: cost, path_len, path [nq, path_cap]
     (cells x*H+y, start -> goal), n_expanded (len(EXPAND)), status (1 = extractPath gave up after
     1000 steps, 4 = the reference raises), optional counters [nq, 4]."""
-    torch = _lib.device_check()
-    L = _lib.load_library()
-    ctx = _lib.context()
-    occ = np.asarray(occ)
-    W, H = occ.shape
-    occ_bits = occ_bits_device(occ, torch)
-    s = _dev(torch, starts, torch.int32).reshape(-1, 2)
-    g = _dev(torch, goals, torch.int32).reshape(-1, 2)
-    nq = int(s.shape[0])
-    out = dict(cost=torch.empty(nq, dtype=torch.float64, device="cuda"),
-               path_len=torch.empty(nq, dtype=torch.int32, device="cuda"),
-               path=torch.empty((nq, int(path_cap)), dtype=torch.int32, device="cuda"),
-               n_expanded=torch.empty(nq, dtype=torch.int32, device="cuda"),
-               status=torch.empty(nq, dtype=torch.int32, device="cuda"))
-    out["counters"] = torch.empty((nq, 4), dtype=torch.int64, device="cuda") if counters else None
+    torch, L, ctx = _open()
+    occ_bits, W, H = _occ2d(torch, occ)
+    s, g, nq = _endpoints(torch, starts, goals, 2, torch.int32)
+    path_cap = int(path_cap)
+    out = _records(torch, (nq,), path_cap, counters=counters)
     fn = L.pmp_dstarlite2d_batch if lite else L.pmp_lpastar2d_batch
-    rc = fn(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), W, H,
-                               1 if heuristic == "manhattan" else 0, s.data_ptr(), g.data_ptr(), nq,
-                               out["cost"].data_ptr(), out["path_len"].data_ptr(), out["path"].data_ptr(),
-                               int(path_cap), out["n_expanded"].data_ptr(), _lib.ptr(out["counters"]),
-                               out["status"].data_ptr())
+    rc = fn(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), W, H, _manhattan(heuristic), s.data_ptr(), g.data_ptr(), nq,
+            out["cost"].data_ptr(), out["path_len"].data_ptr(), out["path"].data_ptr(), path_cap,
+            out["n_expanded"].data_ptr(), _lib.ptr(out["counters"]), out["status"].data_ptr())
     _lib.check(ctx, rc, "pmp_dstarlite2d_batch" if lite else "pmp_lpastar2d_batch")
     return out
 
@@ -479,33 +516,22 @@ def lpastar2d_replan_batch(occ, starts, goals, toggles, heuristic: str = "euclid
     plan() on the kept state, for every query (pmp_lpastar2d_replan_batch); lite=True: DStarLite.plan()
     then DStarLite.OnPress per toggle (d_star_lite.py:61-97, pmp_dstarlite2d_replan_batch).  toggles [nq, nt, 2].
     Returns cost / n_expanded / status [nq, nt + 1] (status -1 = not run) and the last plan's path."""
-    torch = _lib.device_check()
-    L = _lib.load_library()
-    ctx = _lib.context()
-    occ = np.asarray(occ)
-    W, H = occ.shape
-    occ_bits = occ_bits_device(occ, torch)
-    s = _dev(torch, starts, torch.int32).reshape(-1, 2)
-    g = _dev(torch, goals, torch.int32).reshape(-1, 2)
-    nq = int(s.shape[0])
+    torch, L, ctx = _open()
+    occ_bits, W, H = _occ2d(torch, occ)
+    s, g, nq = _endpoints(torch, starts, goals, 2, torch.int32)
     t = _dev(torch, toggles, torch.int32).reshape(nq, -1, 2)
     nt = int(t.shape[1])
     if nt < 1:
         raise ValueError("lpastar2d_replan_batch needs at least one toggle per query")
     if bool(((t[..., 0] < 0) | (t[..., 0] >= W) | (t[..., 1] < 0) | (t[..., 1] >= H)).any()):
         raise ValueError("toggle cells must lie in the grid (OnPress rejects others, lpa_star.py:108-109)")
-    out = dict(cost=torch.empty((nq, nt + 1), dtype=torch.float64, device="cuda"),
-               n_expanded=torch.empty((nq, nt + 1), dtype=torch.int32, device="cuda"),
-               status=torch.empty((nq, nt + 1), dtype=torch.int32, device="cuda"),
-               path_len=torch.empty(nq, dtype=torch.int32, device="cuda"),
-               path=torch.empty((nq, int(path_cap)), dtype=torch.int32, device="cuda"))
-    out["counters"] = torch.empty((nq, 4), dtype=torch.int64, device="cuda") if counters else None
+    path_cap = int(path_cap)
+    # a record per plan, but only the last plan's path
+    out = _records(torch, (nq, nt + 1), path_cap, path_lead=(nq,), counters=counters)
     fn = L.pmp_dstarlite2d_replan_batch if lite else L.pmp_lpastar2d_replan_batch
-    rc = fn(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), W, H,
-                                      1 if heuristic == "manhattan" else 0, s.data_ptr(), g.data_ptr(), nq,
-                                      t.data_ptr(), nt, out["cost"].data_ptr(), out["n_expanded"].data_ptr(),
-                                      out["status"].data_ptr(), out["path_len"].data_ptr(), out["path"].data_ptr(),
-                                      int(path_cap), _lib.ptr(out["counters"]))
+    rc = fn(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), W, H, _manhattan(heuristic), s.data_ptr(), g.data_ptr(), nq,
+            t.data_ptr(), nt, out["cost"].data_ptr(), out["n_expanded"].data_ptr(), out["status"].data_ptr(),
+            out["path_len"].data_ptr(), out["path"].data_ptr(), path_cap, _lib.ptr(out["counters"]))
     _lib.check(ctx, rc, "pmp_dstarlite2d_replan_batch" if lite else "pmp_lpastar2d_replan_batch")
     return out
 
@@ -521,6 +547,33 @@ def map_arrays(env, torch=None):
     return t(env.obs_rect, 4), t(env.obs_circ, 3), t(env.boundary, 4)
 
 
+def _sample_inputs(torch, env, starts, goals, rnd, sample_num, delta, max_dist, radius, goal_sample_rate, star):
+    """What the three sampling wrappers take in: the Map's obstacle arrays, the endpoints and the random
+    streams on the device, and the RRTParams.  Returns (head, keep, nq, rnd): head is what their C entries
+    take after the context and the stream, from the parameters to the goals; keep = (rect, circ, bnd, s, g)
+    are the tensors head points into, to be held until the launch; rnd is [nq, stride]."""
+    rect, circ, bnd = map_arrays(env, torch)
+    s, g, nq = _endpoints(torch, starts, goals, 2, torch.float64)
+    rnd = _dev(torch, rnd, torch.float64).reshape(nq, -1)
+    P = _lib.RRTParams(float(env.x_range), float(env.y_range), float(delta), float(max_dist), float(radius),
+                       float(goal_sample_rate), int(sample_num), int(star))
+    head = (ctypes.byref(P), rect.data_ptr(), int(rect.shape[0]), circ.data_ptr(), int(circ.shape[0]), bnd.data_ptr(),
+            int(bnd.shape[0]), s.data_ptr(), g.data_ptr())
+    return head, (rect, circ, bnd, s, g), nq, rnd
+
+
+def _tree_outputs(torch, nq, trees, cap, path_cap, counters):
+    """What the three sampling wrappers give back: the tree block with the per-tree leading shape `trees`
+    (() for one tree per query, (2,) for RRT-Connect's pair), the path and the per-query scalars."""
+    f64 = dict(dtype=torch.float64, device="cuda")
+    i32 = dict(dtype=torch.int32, device="cuda")
+    return dict(tree_xy=torch.empty(nq, *trees, cap, 2, **f64), tree_g=torch.empty(nq, *trees, cap, **f64),
+                tree_parent=torch.empty(nq, *trees, cap, **i32), n_nodes=torch.empty(nq, *trees, **i32),
+                path_len=torch.empty(nq, **i32), path=torch.empty(nq, max(path_cap, 1), 2, **f64),
+                draws=torch.empty(nq, dtype=torch.int64, device="cuda"), status=torch.empty(nq, **i32),
+                counters=torch.zeros(nq, 4, dtype=torch.int64, device="cuda") if counters else None)
+
+
 def rrt_batch(env, starts, goals, rnd, sample_num: int, star: bool = True, max_dist: float = 0.5,
               radius: float = 10.0, goal_sample_rate: float = 0.05, delta: float = 0.5, path_cap: int | None = None,
               counters: bool = False):
@@ -528,29 +581,14 @@ def rrt_batch(env, starts, goals, rnd, sample_num: int, star: bool = True, max_d
     rnd: [nq, stride] f64 random streams (RandomState.random_sample order; 3*sample_num+1 per query).
     Returns dict of device tensors: tree_xy [nq,cap,2], tree_g, tree_parent, n_nodes, cost, path_len,
     path [nq,path_cap,2] (goal -> start), draws, status."""
-    torch = _lib.device_check()
-    L = _lib.load_library()
-    ctx = _lib.context()
-    rect, circ, bnd = map_arrays(env, torch)
-    s = _dev(torch, starts, torch.float64).reshape(-1, 2)
-    g = _dev(torch, goals, torch.float64).reshape(-1, 2)
-    nq = int(s.shape[0])
-    rnd = _dev(torch, rnd, torch.float64).reshape(nq, -1)
+    torch, L, ctx = _open()
+    head, keep, nq, rnd = _sample_inputs(torch, env, starts, goals, rnd, sample_num, delta, max_dist, radius,
+                                         goal_sample_rate, bool(star))
     cap = int(sample_num) + 2
     path_cap = cap if path_cap is None else int(path_cap)
-    f64 = dict(dtype=torch.float64, device="cuda")
-    i32 = dict(dtype=torch.int32, device="cuda")
-    out = dict(tree_xy=torch.empty((nq, cap, 2), **f64), tree_g=torch.empty((nq, cap), **f64),
-               tree_parent=torch.empty((nq, cap), **i32), n_nodes=torch.empty(nq, **i32),
-               cost=torch.empty(nq, **f64), path_len=torch.empty(nq, **i32),
-               path=torch.empty((nq, max(path_cap, 1), 2), **f64), draws=torch.empty(nq, dtype=torch.int64, device="cuda"),
-               status=torch.empty(nq, **i32),
-               counters=torch.zeros((nq, 4), dtype=torch.int64, device="cuda") if counters else None)
-    P = _lib.RRTParams(float(env.x_range), float(env.y_range), float(delta), float(max_dist), float(radius),
-                       float(goal_sample_rate), int(sample_num), int(bool(star)))
-    rc = L.pmp_rrt_batch(ctx, _lib.stream_ptr(), ctypes.byref(P), rect.data_ptr(),
-                         int(rect.shape[0]), circ.data_ptr(), int(circ.shape[0]), bnd.data_ptr(), int(bnd.shape[0]),
-                         s.data_ptr(), g.data_ptr(), nq, rnd.data_ptr(), int(rnd.shape[1]), cap,
+    out = _tree_outputs(torch, nq, (), cap, path_cap, counters)
+    out["cost"] = torch.empty(nq, dtype=torch.float64, device="cuda")
+    rc = L.pmp_rrt_batch(ctx, _lib.stream_ptr(), *head, nq, rnd.data_ptr(), int(rnd.shape[1]), cap,
                          out["tree_xy"].data_ptr(), out["tree_g"].data_ptr(), out["tree_parent"].data_ptr(),
                          out["n_nodes"].data_ptr(), out["cost"].data_ptr(), out["path_len"].data_ptr(),
                          out["path"].data_ptr(), path_cap, out["draws"].data_ptr(), out["status"].data_ptr(),
@@ -583,30 +621,18 @@ def informed_rrt_batch(env, starts, goals, rnd, sample_num: int, max_dist: float
     Returns dict of device tensors: tree_xy [nq,cap,2], tree_g, tree_parent, n_nodes, best_cost (inf:
     never connected), n_finds, goal_slot (-1: never connected), path_len, path [nq,path_cap,2] (the best
     connection's, goal -> start), draws, status."""
-    torch = _lib.device_check()
-    L = _lib.load_library()
-    ctx = _lib.context()
-    rect, circ, bnd = map_arrays(env, torch)
-    s = _dev(torch, starts, torch.float64).reshape(-1, 2)
-    g = _dev(torch, goals, torch.float64).reshape(-1, 2)
+    torch, L, ctx = _open()
+    head, keep, nq, rnd = _sample_inputs(torch, env, starts, goals, rnd, sample_num, delta, max_dist, radius,
+                                         goal_sample_rate, 1)
+    s, g = keep[3:]
     ell = torch.as_tensor(ellipse_constants(s.cpu().numpy(), g.cpu().numpy()), device="cuda")
-    nq = int(s.shape[0])
-    rnd = _dev(torch, rnd, torch.float64).reshape(nq, -1)
     cap = int(sample_num) + 2
     path_cap = cap if path_cap is None else int(path_cap)
-    f64 = dict(dtype=torch.float64, device="cuda")
-    i32 = dict(dtype=torch.int32, device="cuda")
-    out = dict(tree_xy=torch.empty((nq, cap, 2), **f64), tree_g=torch.empty((nq, cap), **f64),
-               tree_parent=torch.empty((nq, cap), **i32), n_nodes=torch.empty(nq, **i32),
-               best_cost=torch.empty(nq, **f64), n_finds=torch.empty(nq, **i32), goal_slot=torch.empty(nq, **i32),
-               path_len=torch.empty(nq, **i32), path=torch.empty((nq, max(path_cap, 1), 2), **f64),
-               draws=torch.empty(nq, dtype=torch.int64, device="cuda"), status=torch.empty(nq, **i32),
-               counters=torch.zeros((nq, 4), dtype=torch.int64, device="cuda") if counters else None)
-    P = _lib.RRTParams(float(env.x_range), float(env.y_range), float(delta), float(max_dist), float(radius),
-                       float(goal_sample_rate), int(sample_num), 1)
-    rc = L.pmp_informed_rrt_batch(ctx, _lib.stream_ptr(), ctypes.byref(P), rect.data_ptr(), int(rect.shape[0]),
-                                  circ.data_ptr(), int(circ.shape[0]), bnd.data_ptr(), int(bnd.shape[0]),
-                                  s.data_ptr(), g.data_ptr(), ell.data_ptr(), nq, rnd.data_ptr(), int(rnd.shape[1]),
+    out = _tree_outputs(torch, nq, (), cap, path_cap, counters)
+    out.update(best_cost=torch.empty(nq, dtype=torch.float64, device="cuda"),
+               n_finds=torch.empty(nq, dtype=torch.int32, device="cuda"),
+               goal_slot=torch.empty(nq, dtype=torch.int32, device="cuda"))
+    rc = L.pmp_informed_rrt_batch(ctx, _lib.stream_ptr(), *head, ell.data_ptr(), nq, rnd.data_ptr(), int(rnd.shape[1]),
                                   cap, out["tree_xy"].data_ptr(), out["tree_g"].data_ptr(),
                                   out["tree_parent"].data_ptr(), out["n_nodes"].data_ptr(),
                                   out["best_cost"].data_ptr(), out["n_finds"].data_ptr(), out["goal_slot"].data_ptr(),
@@ -635,30 +661,16 @@ def rrt_connect_batch(env, starts, goals, rnd, sample_num: int, max_dist: float 
     Returns dict of device tensors: tree_xy [nq,2,cap,2], tree_g, tree_parent [nq,2,cap] (tree 0 rooted at
     the start, tree 1 at the goal), n_nodes [nq,2], forward, boundary [nq,2], cost, path_len, path
     [nq,path_cap,2] (start -> goal), iters, draws, status."""
-    torch = _lib.device_check()
-    L = _lib.load_library()
-    ctx = _lib.context()
-    rect, circ, bnd = map_arrays(env, torch)
-    s = _dev(torch, starts, torch.float64).reshape(-1, 2)
-    g = _dev(torch, goals, torch.float64).reshape(-1, 2)
-    nq = int(s.shape[0])
-    rnd = _dev(torch, rnd, torch.float64).reshape(nq, -1)
+    torch, L, ctx = _open()
+    head, keep, nq, rnd = _sample_inputs(torch, env, starts, goals, rnd, sample_num, delta, max_dist, 0.0,
+                                         goal_sample_rate, 0)
     cap = RRT_CONNECT_DEFAULT_CAP if cap is None else int(cap)
     path_cap = 2 * cap if path_cap is None else int(path_cap)
-    f64 = dict(dtype=torch.float64, device="cuda")
+    out = _tree_outputs(torch, nq, (2,), cap, path_cap, counters)
     i32 = dict(dtype=torch.int32, device="cuda")
-    out = dict(tree_xy=torch.empty((nq, 2, cap, 2), **f64), tree_g=torch.empty((nq, 2, cap), **f64),
-               tree_parent=torch.empty((nq, 2, cap), **i32), n_nodes=torch.empty((nq, 2), **i32),
-               forward=torch.empty(nq, **i32), boundary=torch.empty((nq, 2), **i32), cost=torch.empty(nq, **f64),
-               path_len=torch.empty(nq, **i32), path=torch.empty((nq, max(path_cap, 1), 2), **f64),
-               iters=torch.empty(nq, **i32), draws=torch.empty(nq, dtype=torch.int64, device="cuda"),
-               status=torch.empty(nq, **i32),
-               counters=torch.zeros((nq, 4), dtype=torch.int64, device="cuda") if counters else None)
-    P = _lib.RRTParams(float(env.x_range), float(env.y_range), float(delta), float(max_dist), 0.0,
-                       float(goal_sample_rate), int(sample_num), 0)
-    rc = L.pmp_rrt_connect_batch(ctx, _lib.stream_ptr(), ctypes.byref(P), rect.data_ptr(), int(rect.shape[0]),
-                                 circ.data_ptr(), int(circ.shape[0]), bnd.data_ptr(), int(bnd.shape[0]),
-                                 s.data_ptr(), g.data_ptr(), nq, rnd.data_ptr(), int(rnd.shape[1]), cap,
+    out.update(cost=torch.empty(nq, dtype=torch.float64, device="cuda"), forward=torch.empty(nq, **i32),
+               boundary=torch.empty(nq, 2, **i32), iters=torch.empty(nq, **i32))
+    rc = L.pmp_rrt_connect_batch(ctx, _lib.stream_ptr(), *head, nq, rnd.data_ptr(), int(rnd.shape[1]), cap,
                                  out["tree_xy"].data_ptr(), out["tree_g"].data_ptr(), out["tree_parent"].data_ptr(),
                                  out["n_nodes"].data_ptr(), out["forward"].data_ptr(), out["boundary"].data_ptr(),
                                  out["cost"].data_ptr(), out["path_len"].data_ptr(), out["path"].data_ptr(), path_cap,
@@ -677,31 +689,13 @@ def astar3d_batch(occ, starts, goals, heuristic: str = "euclidean", path_cap: in
     Returns dict of device tensors: cost (inf if unreachable), path_len, path [nq, path_cap]
     (cells (x*Y+y)*Z+z, start -> goal), n_expanded (len(CLOSED)), status, optional expand / counters.
     """
-    torch = _lib.device_check()
-    L = _lib.load_library()
-    ctx = _lib.context()
-    occ = np.asarray(occ)
-    per_query = occ.ndim == 4
-    X, Y, Z = occ.shape[-3:]
-    if per_query:
-        words = np.stack([pack_bits(o) for o in occ])
-    else:
-        words = pack_bits(occ)
-    occ_bits = torch.as_tensor(np.ascontiguousarray(words).view(np.int32), device="cuda")
-    s = _dev(torch, starts, torch.int32).reshape(-1, 3)
-    g = _dev(torch, goals, torch.int32).reshape(-1, 3)
-    nq = int(s.shape[0])
-    if path_cap is None:
-        path_cap = min(X * Y * Z + 1, 1 << 16)
-    out = dict(cost=torch.empty(nq, dtype=torch.float64, device="cuda"),
-               path_len=torch.empty(nq, dtype=torch.int32, device="cuda"),
-               path=torch.empty((nq, path_cap), dtype=torch.int32, device="cuda"),
-               n_expanded=torch.empty(nq, dtype=torch.int32, device="cuda"),
-               status=torch.empty(nq, dtype=torch.int32, device="cuda"))
-    out["expand"] = torch.empty((nq, expand_cap), dtype=torch.int32, device="cuda") if expand_cap else None
-    out["counters"] = torch.empty((nq, 4), dtype=torch.int64, device="cuda") if counters else None
-    rc = L.pmp_graph3d_batch(ctx, _lib.stream_ptr(), _lib.ALGOS[algo], occ_bits.data_ptr(), 1 if per_query else 0,
-                             X, Y, Z, 1 if heuristic == "manhattan" else 0, s.data_ptr(), g.data_ptr(), nq,
+    torch, L, ctx = _open()
+    occ_bits, per_query, (X, Y, Z) = _occ3d_bits(torch, occ)
+    s, g, nq = _endpoints(torch, starts, goals, 3, torch.int32)
+    path_cap = _path_cap(path_cap, X * Y * Z)
+    out = _records(torch, (nq,), path_cap, expand=expand_cap, counters=counters)
+    rc = L.pmp_graph3d_batch(ctx, _lib.stream_ptr(), _lib.ALGOS[algo], occ_bits.data_ptr(), int(per_query),
+                             X, Y, Z, _manhattan(heuristic), s.data_ptr(), g.data_ptr(), nq,
                              out["cost"].data_ptr(), out["path_len"].data_ptr(), out["path"].data_ptr(), path_cap,
                              out["n_expanded"].data_ptr(), _lib.ptr(out["expand"]), int(expand_cap),
                              _lib.ptr(out["counters"]), out["status"].data_ptr())
@@ -719,26 +713,15 @@ def jps3d_batch(occ, starts, goals, heuristic: str = "euclidean", path_cap: int 
     expand_cap != 0, expand_parent / expand_g [nq, expand_cap]: the final CLOSED parent cell and g of
     the cells in `expand`.
     """
-    torch = _lib.device_check()
-    L = _lib.load_library()
-    ctx = _lib.context()
+    torch, L, ctx = _open()
     occ_bits, per_query, (X, Y, Z) = _occ3d_bits(torch, occ)
-    s = _dev(torch, starts, torch.int32).reshape(-1, 3)
-    g = _dev(torch, goals, torch.int32).reshape(-1, 3)
-    nq = int(s.shape[0])
-    if path_cap is None:
-        path_cap = min(X * Y * Z + 1, 1 << 16)
-    i32 = dict(dtype=torch.int32, device="cuda")
-    out = dict(cost=torch.empty(nq, dtype=torch.float64, device="cuda"), path_len=torch.empty(nq, **i32),
-               path=torch.empty((nq, path_cap), **i32), n_expanded=torch.empty(nq, **i32),
-               status=torch.empty(nq, **i32))
-    out["expand"] = torch.empty((nq, expand_cap), **i32) if expand_cap else None
-    out["expand_parent"] = torch.empty((nq, expand_cap), **i32) if expand_cap else None
-    out["expand_g"] = torch.empty((nq, expand_cap), dtype=torch.float64, device="cuda") if expand_cap else None
-    out["counters"] = torch.empty((nq, 4), dtype=torch.int64, device="cuda") if counters else None
-    rc = L.pmp_jps3d_batch(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), 1 if per_query else 0, X, Y, Z,
-                           1 if heuristic == "manhattan" else 0, s.data_ptr(), g.data_ptr(), nq,
-                           out["cost"].data_ptr(), out["path_len"].data_ptr(), out["path"].data_ptr(), int(path_cap),
+    s, g, nq = _endpoints(torch, starts, goals, 3, torch.int32)
+    path_cap = _path_cap(path_cap, X * Y * Z)
+    out = _records(torch, (nq,), path_cap, expand=expand_cap, expand_parent=expand_cap, expand_g=expand_cap,
+                   counters=counters)
+    rc = L.pmp_jps3d_batch(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), int(per_query), X, Y, Z,
+                           _manhattan(heuristic), s.data_ptr(), g.data_ptr(), nq,
+                           out["cost"].data_ptr(), out["path_len"].data_ptr(), out["path"].data_ptr(), path_cap,
                            out["n_expanded"].data_ptr(), _lib.ptr(out["expand"]), _lib.ptr(out["expand_parent"]),
                            _lib.ptr(out["expand_g"]), int(expand_cap), _lib.ptr(out["counters"]),
                            out["status"].data_ptr())
@@ -760,33 +743,15 @@ def jps2d_batch(occ, starts, goals, heuristic: str = "euclidean", path_cap: int 
     node's parent cell and g; optional counters i64 [nq, 4] (pushes, pops, expansions, max heap size).
     push_cap: pushes (and heap entries) kept per query, 0 = the kernel's default.
     """
-    torch = _lib.device_check()
-    L = _lib.load_library()
-    ctx = _lib.context()
-    if occ_bits is not None:
-        W, H = (int(occ[0]), int(occ[1])) if isinstance(occ, tuple) else (int(occ.shape[0]), int(occ.shape[1]))
-    elif hasattr(occ, "occupancy_words"):  # a Grid
-        W, H = int(occ.x_range), int(occ.y_range)
-        occ_bits = torch.as_tensor(occ.occupancy_words().view(np.int32), device="cuda")
-    else:
-        W, H = int(occ.shape[0]), int(occ.shape[1])
-        occ_bits = occ_bits_device(occ, torch)
-    s = _dev(torch, starts, torch.int32).reshape(-1, 2)
-    g = _dev(torch, goals, torch.int32).reshape(-1, 2)
-    nq = int(s.shape[0])
-    if path_cap is None:
-        path_cap = min(W * H + 1, 1 << 12)
-    i32 = dict(dtype=torch.int32, device="cuda")
-    out = dict(cost=torch.empty(nq, dtype=torch.float64, device="cuda"), path_len=torch.empty(nq, **i32),
-               path=torch.empty((nq, path_cap), **i32), n_expanded=torch.empty(nq, **i32),
-               status=torch.empty(nq, **i32))
-    out["expand"] = torch.empty((nq, expand_cap), **i32) if expand_cap else None
-    out["expand_parent"] = torch.empty((nq, expand_cap), **i32) if expand_cap else None
-    out["expand_g"] = torch.empty((nq, expand_cap), dtype=torch.float64, device="cuda") if expand_cap else None
-    out["counters"] = torch.empty((nq, 4), dtype=torch.int64, device="cuda") if counters else None
-    rc = L.pmp_jps2d_batch(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), W, H, 1 if heuristic == "manhattan" else 0,
+    torch, L, ctx = _open()
+    occ_bits, W, H = _occ2d(torch, occ, occ_bits)
+    s, g, nq = _endpoints(torch, starts, goals, 2, torch.int32)
+    path_cap = _path_cap(path_cap, W * H, 1 << 12)
+    out = _records(torch, (nq,), path_cap, expand=expand_cap, expand_parent=expand_cap, expand_g=expand_cap,
+                   counters=counters)
+    rc = L.pmp_jps2d_batch(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), W, H, _manhattan(heuristic),
                            s.data_ptr(), g.data_ptr(), nq, out["cost"].data_ptr(), out["path_len"].data_ptr(),
-                           out["path"].data_ptr(), int(path_cap), out["n_expanded"].data_ptr(), _lib.ptr(out["expand"]),
+                           out["path"].data_ptr(), path_cap, out["n_expanded"].data_ptr(), _lib.ptr(out["expand"]),
                            _lib.ptr(out["expand_parent"]), _lib.ptr(out["expand_g"]), int(expand_cap), int(push_cap),
                            _lib.ptr(out["counters"]), out["status"].data_ptr())
     _lib.check(ctx, rc, "pmp_jps2d_batch")
@@ -804,13 +769,9 @@ def dstar3d_batch(occ, starts, goals, blocks=None, path_cap: int | None = None, 
     path [nq, R, path_cap] (voxels (x*Y+y)*Z+z, start -> goal), n_process [nq, R] (len(EXPAND)),
     status [nq, R] (include/pmp.h), optional expand [nq, expand_cap] (plan()'s EXPAND voxels).
     occ_bits: optional device words of `occ` already packed (occ may then be just its shape)."""
-    torch = _lib.device_check()
-    L = _lib.load_library()
-    ctx = _lib.context()
+    torch, L, ctx = _open()
     occ_bits, per_query, (X, Y, Z) = _occ3d_bits(torch, occ, occ_bits)
-    s = _dev(torch, starts, torch.int32).reshape(-1, 3)
-    g = _dev(torch, goals, torch.int32).reshape(-1, 3)
-    nq = int(s.shape[0])
+    s, g, nq = _endpoints(torch, starts, goals, 3, torch.int32)
     if blocks is None:
         nr, nb, b = 0, 0, None
     else:
@@ -818,32 +779,15 @@ def dstar3d_batch(occ, starts, goals, blocks=None, path_cap: int | None = None, 
         if b.dim() != 4 or b.shape[0] != nq or b.shape[3] != 3:
             raise ValueError("blocks must be [nq, nrounds, nblk, 3]")
         nr, nb = int(b.shape[1]), int(b.shape[2])
-    R = nr + 1
-    path_cap = min(X * Y * Z + 1, 1 << 16) if path_cap is None else int(path_cap)
-    i32 = dict(dtype=torch.int32, device="cuda")
-    out = dict(cost=torch.empty((nq, R), dtype=torch.float64, device="cuda"), path_len=torch.empty((nq, R), **i32),
-               path=torch.empty((nq, R, path_cap), **i32),
-               n_process=torch.empty((nq, R), dtype=torch.int64, device="cuda"), status=torch.empty((nq, R), **i32))
-    out["expand"] = torch.empty((nq, expand_cap), **i32) if expand_cap else None
-    rc = L.pmp_dstar3d_batch(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), 1 if per_query else 0, X, Y, Z, s.data_ptr(),
+    path_cap = _path_cap(path_cap, X * Y * Z)
+    out = _records(torch, (nq, nr + 1), path_cap, "n_process", "int64", expand=expand_cap)
+    rc = L.pmp_dstar3d_batch(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), int(per_query), X, Y, Z, s.data_ptr(),
                              g.data_ptr(), nq, _lib.ptr(b), nr, nb, out["cost"].data_ptr(), out["path_len"].data_ptr(),
                              out["path"].data_ptr(), path_cap, out["n_process"].data_ptr(), out["status"].data_ptr(),
                              _lib.ptr(out["expand"]), int(expand_cap), int(max_process))
     _lib.check(ctx, rc, "pmp_dstar3d_batch")
     out["dims"] = (X, Y, Z)
     return out
-
-
-def _occ3d_bits(torch, occ, occ_bits=None):
-    """(device words, per_query, (X, Y, Z)) of a shared [X, Y, Z] or per-query [nq, X, Y, Z] grid; with
-    occ_bits given, `occ` only supplies the shape."""
-    shape = tuple(occ) if isinstance(occ, tuple) else np.asarray(occ).shape
-    per_query = len(shape) == 4
-    if occ_bits is None:
-        occ = np.asarray(occ)
-        words = np.stack([pack_bits(o) for o in occ]) if per_query else pack_bits(occ)
-        occ_bits = torch.as_tensor(np.ascontiguousarray(words).view(np.int32), device="cuda")
-    return occ_bits, per_query, tuple(int(d) for d in shape[-3:])
 
 
 def lpastar3d_batch(occ, starts, goals, changes=None, heuristic: str = "euclidean", path_cap: int | None = None,
@@ -855,13 +799,9 @@ def lpastar3d_batch(occ, starts, goals, changes=None, heuristic: str = "euclidea
     path [nq, R, path_cap] (voxels (x*Y+y)*Z+z, start -> goal), n_expanded [nq, R] (len(EXPAND)),
     status [nq, R] (include/pmp.h), optional counters [nq, 4].
     occ_bits: optional device words of `occ` already packed (occ may then be just its shape)."""
-    torch = _lib.device_check()
-    L = _lib.load_library()
-    ctx = _lib.context()
+    torch, L, ctx = _open()
     occ_bits, per_query, (X, Y, Z) = _occ3d_bits(torch, occ, occ_bits)
-    s = _dev(torch, starts, torch.int32).reshape(-1, 3)
-    g = _dev(torch, goals, torch.int32).reshape(-1, 3)
-    nq = int(s.shape[0])
+    s, g, nq = _endpoints(torch, starts, goals, 3, torch.int32)
     if changes is None:
         nr, ch = 0, None
     else:
@@ -869,15 +809,10 @@ def lpastar3d_batch(occ, starts, goals, changes=None, heuristic: str = "euclidea
         if ch.dim() != 3 or ch.shape[0] != nq or ch.shape[2] != 4:
             raise ValueError("changes must be [nq, nr, 4]")
         nr = int(ch.shape[1])
-    R = nr + 1
-    path_cap = min(X * Y * Z + 1, 1 << 16) if path_cap is None else int(path_cap)
-    i32 = dict(dtype=torch.int32, device="cuda")
-    out = dict(cost=torch.empty((nq, R), dtype=torch.float64, device="cuda"), path_len=torch.empty((nq, R), **i32),
-               path=torch.empty((nq, R, path_cap), **i32),
-               n_expanded=torch.empty((nq, R), dtype=torch.int64, device="cuda"), status=torch.empty((nq, R), **i32))
-    out["counters"] = torch.empty((nq, 4), dtype=torch.int64, device="cuda") if counters else None
-    rc = L.pmp_lpastar3d_batch(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), 1 if per_query else 0, X, Y, Z,
-                               1 if heuristic == "manhattan" else 0, s.data_ptr(), g.data_ptr(), nq, _lib.ptr(ch), nr,
+    path_cap = _path_cap(path_cap, X * Y * Z)
+    out = _records(torch, (nq, nr + 1), path_cap, "n_expanded", "int64", counters=counters)
+    rc = L.pmp_lpastar3d_batch(ctx, _lib.stream_ptr(), occ_bits.data_ptr(), int(per_query), X, Y, Z,
+                               _manhattan(heuristic), s.data_ptr(), g.data_ptr(), nq, _lib.ptr(ch), nr,
                                out["cost"].data_ptr(), out["path_len"].data_ptr(), out["path"].data_ptr(), path_cap,
                                out["n_expanded"].data_ptr(), out["status"].data_ptr(), _lib.ptr(out["counters"]),
                                int(max_expansions))

@@ -15,6 +15,16 @@ from .env import Grid, Node
 from .planner import Planner
 
 
+def cells_xy(cells, H: int) -> list:
+    """Cell ids x*H + y -> [(x, y), ...] of Python ints."""
+    return [(int(c) // H, int(c) % H) for c in cells]
+
+
+def cells_xyz(cells, Y: int, Z: int) -> list:
+    """Voxel ids (x*Y + y)*Z + z -> [(x, y, z), ...] of Python ints."""
+    return [(int(c) // (Y * Z), (int(c) // Z) % Y, int(c) % Z) for c in cells]
+
+
 class LazyExpand(Sequence):
     """The CLOSED Node list of a plan, built on first access (AStar.lazy_expand = True): len() is
     known without building it."""
@@ -122,13 +132,13 @@ class AStar(GraphSearcher):
                                          expand_cap=expand_cap, algo=self._algo, occ_bits=cached[2])
             st, nexp, plen = (int(v) for v in torch.stack([r["status"][0], r["n_expanded"][0],
                                                             r["path_len"][0]]).cpu().tolist())
-            cells = r["path"][0, :plen].cpu().numpy()
-            exp = r["expand"][0, :nexp].cpu().numpy().astype(np.uint32)
+            cells = batch.query0(r, "path", plen)
+            exp = batch.query0(r, "expand", nexp).astype(np.uint32)
         if st != 0:
             if st == 1:
                 return [], [], []
             raise RuntimeError(f"{self} kernel status {st}")
-        path = [(int(c) // H, int(c) % H) for c in cells]
+        path = cells_xy(cells, H)
         cost = 0
         for a, b in zip(path[:-1], path[1:]):
             cost += math.hypot(b[0] - a[0], b[1] - a[1])
@@ -268,16 +278,14 @@ class JPS(AStar):
             return [], [], []
         if st != 0:
             raise RuntimeError(f"{self} kernel status {st}")
-        dec = lambda c: (int(c) // H, int(c) % H)  # noqa: E731
-        path = [dec(c) for c in r["path"][0, :plen].cpu().numpy()]
         expand = []
-        for c, p, gv in zip(r["expand"][0, :ne].cpu().numpy(), r["expand_parent"][0, :ne].cpu().numpy(),
-                            r["expand_g"][0, :ne].cpu().numpy()):
-            node = Node(dec(c), dec(p), float(gv), 0)
+        for c, p, gv in zip(cells_xy(batch.query0(r, "expand", ne), H),
+                            cells_xy(batch.query0(r, "expand_parent", ne), H), batch.query0(r, "expand_g", ne)):
+            node = Node(c, p, float(gv), 0)
             if len(expand):
                 node.h = self.h(node, self.goal)
             expand.append(node)
-        return float(r["cost"][0]), path, expand
+        return float(r["cost"][0]), cells_xy(batch.query0(r, "path", plen), H), expand
 
     @classmethod
     def plan_batch(cls, occ, starts, goals, heuristic_type: str = "euclidean", **kw):
@@ -310,9 +318,7 @@ class LPAStar(GraphSearcher):
             return float(r["cost"][0]), [], None
         if st != 0:
             raise RuntimeError(f"{self} kernel status {st}")
-        plen = int(r["path_len"][0])
-        cells = r["path"][0, :plen].cpu().numpy()
-        return float(r["cost"][0]), [(int(c) // H, int(c) % H) for c in cells], None
+        return float(r["cost"][0]), cells_xy(batch.query0(r, "path", int(r["path_len"][0])), H), None
 
 
 class DStarLite(LPAStar):
@@ -363,8 +369,7 @@ class DStar(GraphSearcher):
             raise AttributeError("'NoneType' object has no attribute 'k'")
         if st != 0:
             raise RuntimeError(f"D* kernel status {st}")
-        cells = r["path"][0, : int(r["path_len"][0])].cpu().numpy()
-        return float(r["cost"][0]), [(int(c) // H, int(c) % H) for c in cells], None
+        return float(r["cost"][0]), cells_xy(batch.query0(r, "path", int(r["path_len"][0])), H), None
 
     def run(self):
         return self.plan()
@@ -402,7 +407,7 @@ class DStar(GraphSearcher):
             raise RuntimeError(f"D* kernel status {st} (a walk or repair the reference never finishes)")
         n = int(r["path_len"][0, k])
         self.cost = float(r["cost"][0, k])
-        self.path = [(int(c) // H, int(c) % H) for c in r["path"][0, k, :n].cpu().numpy()]
+        self.path = cells_xy(batch.query0(r, "path", n, k), H)
         self.EXPAND = [None] * int(r["n_process"][0, k])
 
     @staticmethod
@@ -460,15 +465,12 @@ class AStar3D(GraphSearcher3D):
                                 self.heuristic_type, path_cap=X * Y * Z + 1, expand_cap=X * Y * Z, algo=self._algo)
         st = int(r["status"][0])
         ne = int(r["n_expanded"][0])
-        ex = r["expand"][0, :ne].cpu().numpy()
-        expand = [Node3D((int(c) // (Y * Z), (int(c) // Z) % Y, int(c) % Z), None, None, None) for c in ex]
+        expand = [Node3D(c, None, None, None) for c in cells_xyz(batch.query0(r, "expand", ne), Y, Z)]
         if st == 1:
             return float("inf"), [], expand
         if st != 0:
             raise RuntimeError(f"{self} kernel status {st}")
-        cells = r["path"][0, : int(r["path_len"][0])].cpu().numpy()
-        path = [(int(c) // (Y * Z), (int(c) // Z) % Y, int(c) % Z) for c in cells]
-        return float(r["cost"][0]), path, expand
+        return float(r["cost"][0]), cells_xyz(batch.query0(r, "path", int(r["path_len"][0])), Y, Z), expand
 
     @classmethod
     def plan_batch(cls, occ, starts, goals, heuristic_type: str = "euclidean", **kw):
@@ -545,21 +547,17 @@ class JPS3D(GraphSearcher3D):
                               self.heuristic_type, path_cap=X * Y * Z + 1, expand_cap=X * Y * Z)
         st = int(r["status"][0])
         ne = int(r["n_expanded"][0])
-        dec = lambda c: (int(c) // (Y * Z), (int(c) // Z) % Y, int(c) % Z)  # noqa: E731
-        ex = r["expand"][0, :ne].cpu().numpy()
-        ep = r["expand_parent"][0, :ne].cpu().numpy()
-        eg = r["expand_g"][0, :ne].cpu().numpy()
         expand = []
-        for c, p, g in zip(ex, ep, eg):
-            node = Node3D(dec(c), dec(p), float(g), 0)
+        for c, p, g in zip(cells_xyz(batch.query0(r, "expand", ne), Y, Z),
+                           cells_xyz(batch.query0(r, "expand_parent", ne), Y, Z), batch.query0(r, "expand_g", ne)):
+            node = Node3D(c, p, float(g), 0)
             node.h = self.h(node, self.goal)
             expand.append(node)
         if st == 1:
             return float("inf"), [], expand
         if st != 0:
             raise RuntimeError(f"{self} kernel status {st}")
-        cells = r["path"][0, : int(r["path_len"][0])].cpu().numpy()
-        return float(r["cost"][0]), [dec(c) for c in cells], expand
+        return float(r["cost"][0]), cells_xyz(batch.query0(r, "path", int(r["path_len"][0])), Y, Z), expand
 
     @classmethod
     def plan_batch(cls, occ, starts, goals, heuristic_type: str = "euclidean", **kw):
@@ -619,9 +617,7 @@ class DStar3D(GraphSearcher3D):
         return r
 
     def _cells(self, r, k):
-        X, Y, Z = r["dims"]
-        n = int(r["path_len"][0, k])
-        return [(int(c) // (Y * Z), (int(c) // Z) % Y, int(c) % Z) for c in r["path"][0, k, :n].cpu().numpy()]
+        return cells_xyz(batch.query0(r, "path", int(r["path_len"][0, k]), k), *r["dims"][1:])
 
     def plan(self) -> tuple:
         """(cost, path start->goal, EXPAND) (d_star3d.py:100-109).  An unreachable start gives
@@ -630,10 +626,8 @@ class DStar3D(GraphSearcher3D):
         self._occ0 = self.env.occupancy()
         self._rounds = []
         r = self._run(True)
-        ne = int(r["n_process"][0, 0])
-        X, Y, Z = r["dims"]
-        ex = r["expand"][0, :ne].cpu().numpy()
-        self.EXPAND = [DNode3D((int(c) // (Y * Z), (int(c) // Z) % Y, int(c) % Z), None, None, None, None) for c in ex]
+        voxels = cells_xyz(batch.query0(r, "expand", int(r["n_process"][0, 0])), *r["dims"][1:])
+        self.EXPAND = [DNode3D(c, None, None, None, None) for c in voxels]
         return float(r["cost"][0, 0]), self._cells(r, 0), list(self.EXPAND)
 
     def apply_dynamic_obstacles(self, newly_blocked) -> tuple:
@@ -695,9 +689,7 @@ class LPAStar3D(GraphSearcher3D):
         st = int(r["status"][0, k])
         if st not in (0, 1):
             raise RuntimeError(f"{self} kernel status {st}")
-        n = int(r["path_len"][0, k])
-        cells = r["path"][0, k, :n].cpu().numpy()
-        path = [(int(c) // (Y * Z), (int(c) // Z) % Y, int(c) % Z) for c in cells]
+        path = cells_xyz(batch.query0(r, "path", int(r["path_len"][0, k]), k), Y, Z)
         self.EXPAND = [None] * int(r["n_expanded"][0, k])
         return float(r["cost"][0, k]), path, self.EXPAND
 

@@ -25,6 +25,20 @@ def random_stream(sample_num: int, state=None) -> np.ndarray:
     return rs.random_sample(3 * int(sample_num) + 1)
 
 
+def _tree_nodes(out, n: int, t=None):
+    """(nodes, g, parent): the first n nodes of query 0's tree (t: which of RRT-Connect's two) as
+    Node(current, the parent's coordinates, g, 0), and the g and parent-index columns they were built from."""
+    xy, g, par = (batch.query0(out, k, n, t) for k in ("tree_xy", "tree_g", "tree_parent"))
+    nodes = [Node((float(xy[i, 0]), float(xy[i, 1])), (float(xy[par[i], 0]), float(xy[par[i], 1])), float(g[i]), 0)
+             for i in range(n)]
+    return nodes, g, par
+
+
+def _path_points(out) -> list:
+    """Query 0's path as [(x, y), ...] of Python floats."""
+    return [(float(x), float(y)) for x, y in batch.query0(out, "path", int(out["path_len"][0]))]
+
+
 class SampleSearcher(Planner):
     """global_planner/sample_search/sample_search.py:13-135 (collision tests run on the device)."""
 
@@ -62,13 +76,7 @@ class RRT(SampleSearcher):
         if st not in (0, 1):
             raise RuntimeError(f"RRT kernel status {st}")
         n = int(out["n_nodes"][0])
-        xy = out["tree_xy"][0, :n].cpu().numpy()
-        g = out["tree_g"][0, :n].cpu().numpy()
-        par = out["tree_parent"][0, :n].cpu().numpy()
-        expand = []
-        for i in range(n):
-            cur = (float(xy[i, 0]), float(xy[i, 1]))
-            expand.append(Node(cur, (float(xy[par[i], 0]), float(xy[par[i], 1])), float(g[i]), 0))
+        expand, g, par = _tree_nodes(out, n)
         # the start and goal keep the caller's coordinates (ints in the README examples)
         expand[0] = self.start
         if st == 1:
@@ -76,9 +84,7 @@ class RRT(SampleSearcher):
         self.goal.parent = expand[int(par[n - 1])].current
         self.goal.g = float(g[n - 1])
         expand[-1] = self.goal
-        plen = int(out["path_len"][0])
-        pts = out["path"][0, :plen].cpu().numpy()
-        path = [(float(x), float(y)) for x, y in pts]
+        path = _path_points(out)
         path[0], path[-1] = self.goal.current, self.start.current
         return float(out["cost"][0]), path, expand
 
@@ -150,13 +156,7 @@ class InformedRRT(RRTStar):
             raise RuntimeError(f"Informed RRT* kernel status {st}")
         if draws:
             np.random.random_sample(draws)  # advance the global RNG exactly as the reference's loop does
-        xy = out["tree_xy"][0, :n].cpu().numpy()
-        g = out["tree_g"][0, :n].cpu().numpy()
-        par = out["tree_parent"][0, :n].cpu().numpy()
-        expand = []
-        for i in range(n):
-            cur = (float(xy[i, 0]), float(xy[i, 1]))
-            expand.append(Node(cur, (float(xy[par[i], 0]), float(xy[par[i], 1])), float(g[i]), 0))
+        expand, g, par = _tree_nodes(out, n)
         # the start and goal keep the caller's coordinates (ints in the README examples)
         expand[0] = self.start
         if st == 1:
@@ -165,9 +165,7 @@ class InformedRRT(RRTStar):
         self.goal.parent = expand[int(par[gs])].current
         self.goal.g = float(g[gs])
         expand[gs] = self.goal
-        plen = int(out["path_len"][0])
-        pts = out["path"][0, :plen].cpu().numpy()
-        path = [(float(x), float(y)) for x, y in pts]
+        path = _path_points(out)
         path[0], path[-1] = self.goal.current, self.start.current
         self.c_best = float(out["best_cost"][0])
         return self.c_best, path, expand
@@ -217,12 +215,7 @@ class RRTConnect(RRT):
         roots = (self.start, self.goal)
         trees = []
         for t in (0, 1):
-            n = int(counts[t])
-            xy = out["tree_xy"][0, t, :n].cpu().numpy()
-            g = out["tree_g"][0, t, :n].cpu().numpy()
-            par = out["tree_parent"][0, t, :n].cpu().numpy()
-            nodes = [Node((float(xy[i, 0]), float(xy[i, 1])), (float(xy[par[i], 0]), float(xy[par[i], 1])),
-                          float(g[i]), 0) for i in range(n)]
+            nodes = _tree_nodes(out, int(counts[t]), t)[0]
             # the roots keep the caller's coordinates (ints in the README examples)
             nodes[0] = roots[t]
             trees.append(nodes)
@@ -234,9 +227,7 @@ class RRTConnect(RRT):
                 expand.append(f[k])
             if k < len(b):
                 expand.append(b[k])
-        plen = int(out["path_len"][0])
-        pts = out["path"][0, :plen].cpu().numpy()
-        path = [(float(x), float(y)) for x, y in pts]
+        path = _path_points(out)
         path[0], path[-1] = self.start.current, self.goal.current
         return float(out["cost"][0]), path, expand
 

@@ -11,7 +11,8 @@ import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-from python_motion_planning_amd import _lib, batch, workloads as wl  # noqa: E402
+from python_motion_planning_amd import _lib, workloads as wl  # noqa: E402
+from python_motion_planning_amd.env import pack_bits  # noqa: E402
 
 WARMUP, TIMED, NQ = 5, 20, 8192
 
@@ -22,7 +23,7 @@ def main():
     L, ctx = _lib.load_library(), _lib.context()
     occ, s, g = wl.c5_workload(NQ)
     X, Y, Z = occ.shape[1:]
-    words = np.stack([batch.pack_bits(o) for o in occ])
+    words = np.stack([pack_bits(o) for o in occ])
     occ_d = torch.as_tensor(np.ascontiguousarray(words).view(np.int32), device="cuda")
     s_d, g_d = torch.as_tensor(s, device="cuda"), torch.as_tensor(g, device="cuda")
     cap = X * Y * Z + 1
