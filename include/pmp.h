@@ -733,6 +733,49 @@ int pmp_splinetraj3d_batch(pmp_ctx* ctx, void* stream, const pmp_splinetraj_para
 /* The largest max_waypoints pmp_splinetraj3d_batch accepts (its LDS block within 64 KiB). */
 int pmp_splinetraj3d_max_waypoints(void);
 
+/* Dubins(step, max_curv) (curve_generation/dubins_curve.py:31-33) */
+typedef struct {
+    double step;
+    double max_curv;
+} pmp_dubins_params;
+
+/*
+ * Batched Dubins curves (curve_generation/dubins_curve.py, the `dubins` name of CurveFactory; the steering
+ * function of the nonholonomic sampling planners).  Replaces Dubins(step, max_curv).generation(start, goal)
+ * (:238-313) for n pose pairs: the frame theta / dist / alpha / beta (:253-261, mod2pi as curve.py:51-55,
+ * CPython's hypot), the six words LSL, RSR, LSR, RSL, RLR, LRL in the reference's expressions and order
+ * (:38-205; a word is infeasible when p^2 < 0, for RLR / LRL when |p| > 1), cost |t| + |p| + |q| in
+ * curvature-normalised units (not divided by max_curv, as best_cost is returned), the first strictly
+ * cheapest word (:267-273), the interpolation loop (:283-294: per piece the repeated sum length += step,
+ * not k step; then the piece's exact end), the strip of trailing points whose local x is exactly 0.0
+ * (:301-304: real points too, so equal poses return cost 0 and no point), rotation by theta, translation,
+ * pi2pi on the yaw (:306-311).  Words and counts follow the reference's except where two words tie to
+ * the last bit; values match it to rounding.
+ *   start_xyyaw, goal_xyyaw [n][3] f64: x, y, yaw in radians
+ *   word [n] u8      0..5 = LSL, RSR, LSR, RSL, RLR, LRL; 255 = none
+ *   tpq [n][3]       the word's piece lengths (NaN with word 255); cost [n] (inf with word 255)
+ *   n_points [n]     the reference's len(x_list)
+ *   points [n][point_cap][3] nullable: x, y, yaw of the first min(n_points, point_cap) points; NULL =
+ *       costs and counts only (point_cap then only sizes the table of step sums)
+ *   status [n]  0 ok, 2 point_cap too small (the count is still reported and the first point_cap rows
+ *               are valid; a pair of more than 2^24 steps reports count 0), 4 the reference raises (a
+ *               non-finite pose: no word is chosen and int(nan) raises ValueError) or never ends (a
+ *               coordinate or yaw from about 1e17 on, where mod2pi leaves no angle for pi2pi's loop)
+ * Refused with PMP_EINVAL (the reference never leaves its loop, or divides by zero): step <= 0 or
+ * non-finite, max_curv <= 0 or non-finite.
+ */
+int pmp_dubins_batch(pmp_ctx* ctx, void* stream, const pmp_dubins_params* prm, int n, const double* start_xyyaw,
+                     const double* goal_xyyaw, uint8_t* word, double* tpq, double* cost, int32_t* n_points,
+                     int point_cap, double* points, int32_t* status);
+/*
+ * The Dubins steering metric between every start and every goal: cost [A][B] and word [A][B] of
+ * generation(starts[a], goals[b]) (:253-273) as pmp_dubins_batch computes them, without sampling.  The pair
+ * index is decoded in the kernel; the A B pose pairs are never stored.  cost inf / word 255 where the
+ * reference raises.  Refused with PMP_EINVAL as pmp_dubins_batch (step is checked although unused).
+ */
+int pmp_dubins_cost_matrix(pmp_ctx* ctx, void* stream, const pmp_dubins_params* prm, int A, const double* start_xyyaw,
+                           int B, const double* goal_xyyaw, double* cost, uint8_t* word);
+
 /* Launch-span recording for profiling: while set, every A* 2D launch of this context folds its
  * workers' first start and last end wall-clock ticks into span[0] (atomic min) and span[1] (atomic
  * max); the caller initialises span to {UINT64_MAX, 0}.  NULL switches it off. */

@@ -85,6 +85,8 @@ SIGNATURES = {
     "pmp_splinetraj3d_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                                     _vp, _i, ctypes.c_double, _i]),
     "pmp_splinetraj3d_max_waypoints": (_i, []),
+    "pmp_dubins_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "pmp_dubins_cost_matrix": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
 }
 
 
@@ -191,6 +193,13 @@ class SplineTrajParams(ctypes.Structure):
                    (ctypes.c_double * 3)(*[float(v) for v in max_acceleration]), float(min_time_step),
                    int(spline_degree), 0)
 
+
+class DubinsParams(ctypes.Structure):
+    """pmp_dubins_params == Dubins(step, max_curv) (curve_generation/dubins_curve.py:31-33)."""
+    _fields_ = [("step", ctypes.c_double), ("max_curv", ctypes.c_double)]
+
+
+DUBINS_WORDS = ("LSL", "RSR", "LSR", "RSL", "RLR", "LRL")  # word 0..5, the reference's order (:264)
 
 TRACK_LQR, TRACK_MPC = 0, 1
 

@@ -885,23 +885,36 @@ def _traj3d_batch(torch, arrs, cells, row, min_wp, wp_limit, max_waypoints, eval
         call(o, a, src, nmax, ev, pp)
         return o
 
+    def rerun(redo, idx, pc):
+        sa, sb = pack([arrs[i] for i in redo])[:2] if cells is None else (a[idx].contiguous(), b[idx].contiguous())
+        return launch(sa, sb, {k: None if v is None else v[idx].contiguous() for k, v in pp.items()}, pc)
+
     out = launch(a, b, pp, point_cap)
     if retry_overflow and nq:
-        st = out["status"].cpu().numpy()
-        npt = out["n_points"].cpu().numpy()
-        redo = np.nonzero((st == _lib.STATUS_PATH_OVERFLOW) & (npt > point_cap))[0]
-        if len(redo):
-            pc = int(npt[redo].max())
-            idx = torch.as_tensor(redo, device="cuda", dtype=torch.long)
-            sa, sb = pack([arrs[i] for i in redo])[:2] if cells is None else (a[idx].contiguous(), b[idx].contiguous())
-            r = launch(sa, sb, {k: None if v is None else v[idx].contiguous() for k, v in pp.items()}, pc)
-            big = torch.full((nq, pc, row), float("nan"), dtype=torch.float64, device="cuda")
-            big[:, :point_cap] = out["points"]
-            big[idx] = r["points"]
-            out["points"] = big
-            for k in ("n_points", "total_time", "status") + tuple(merge):
-                out[k][idx] = r[k]
+        _retry_overflowed(torch, out, nq, point_cap, row, rerun, ("total_time",) + tuple(merge))
     return out, off
+
+
+def _retry_overflowed(torch, out, nq, point_cap, row, rerun, merge=()):
+    """The single overflow retry of the wrappers that return point rows (the trajectory generators,
+    dubins_batch).  out: the first launch's outputs with points [nq, point_cap, row], n_points and status.
+    The items whose points overflowed point_cap are run again by rerun(redo, idx, pc) -> the same outputs
+    for those items alone (redo: their indices on the host, idx: on the device, pc: the largest count among
+    them); their rows, n_points, status and the outputs named in merge replace the first run's in out, and
+    points grows to pc, NaN where the first run had no row."""
+    st = out["status"].cpu().numpy()
+    npt = out["n_points"].cpu().numpy()
+    redo = np.nonzero((st == _lib.STATUS_PATH_OVERFLOW) & (npt > point_cap))[0]
+    if len(redo):
+        pc = int(npt[redo].max())
+        idx = torch.as_tensor(redo, device="cuda", dtype=torch.long)
+        r = rerun(redo, idx, pc)
+        big = torch.full((nq, pc, row), float("nan"), dtype=torch.float64, device="cuda")
+        big[:, :point_cap] = out["points"]
+        big[idx] = r["points"]
+        out["points"] = big
+        for k in ("n_points", "status") + tuple(merge):
+            out[k][idx] = r[k]
 
 
 def totp3d_batch(paths, params, point_cap: int | None = None, eval_t=None, retry_overflow: bool = True):
@@ -1047,3 +1060,69 @@ def splinetraj3d_batch(paths, params, point_cap: int | None = None, eval_t=None,
 
     return _traj3d_batch(torch, _xyz_arrays(paths) if cells is None else None, cells, 12, 3, wp_limit,
                          max_waypoints, eval_t, point_cap, estimate, call, retry_overflow)[0]
+
+
+def _dubins_point_cap(torch, s, g, step, max_curv):
+    """An upper bound of a launch's point counts: (hypot max_curv + 4 pi) / step + 6 over its pairs (pairs
+    beyond it are retried; pairs of non-finite poses or of more than 2^24 steps have no points); 2048 where
+    the parameters give none."""
+    if not int(s.shape[0]):
+        return 1
+    if not (step > 0 and max_curv > 0 and math.isfinite(step) and math.isfinite(max_curv)):
+        return 2048  # the entry refuses these
+    est = (torch.hypot(g[:, 0] - s[:, 0], g[:, 1] - s[:, 1]) * max_curv + 4.0 * math.pi) / step + 6.0
+    return int(torch.where(est < float(1 << 24), est, torch.ones_like(est)).max().item())
+
+
+def dubins_batch(starts, goals, step: float, max_curv: float, cost_only: bool = False, point_cap: int | None = None,
+                 retry_overflow: bool = True):
+    """Batched Dubins(step, max_curv).generation(start, goal) (curve_generation/dubins_curve.py:238-313) on
+    pmp_dubins_batch.  starts, goals: [n, 3] poses (x, y, yaw in radians), host arrays or device tensors.
+    Returns dict of device tensors: word [n] u8 (_lib.DUBINS_WORDS; 255 = none), tpq [n, 3], cost [n] (in
+    curvature-normalised units, as the reference returns it), n_points [n], points [n, point_cap, 3] (x, y,
+    yaw; None with cost_only), status (include/pmp.h).  Pairs whose points overflow the first cap are
+    re-run with their exact count when retry_overflow."""
+    torch, L, ctx = _open()
+    s, g, n = _endpoints(torch, starts, goals, 3, torch.float64)
+    if int(g.shape[0]) != n:
+        raise ValueError("starts and goals must have the same length")
+    prm = _lib.DubinsParams(float(step), float(max_curv))
+    if point_cap is None:
+        point_cap = _dubins_point_cap(torch, s, g, prm.step, prm.max_curv)
+    point_cap = max(int(point_cap), 1)
+
+    def launch(s, g, pc):
+        m = int(s.shape[0])
+        f64 = dict(dtype=torch.float64, device="cuda")
+        o = dict(word=torch.empty(m, dtype=torch.uint8, device="cuda"), tpq=torch.empty((m, 3), **f64),
+                 cost=torch.empty(m, **f64), n_points=torch.empty(m, dtype=torch.int32, device="cuda"),
+                 points=None if cost_only else torch.empty((m, pc, 3), **f64),
+                 status=torch.empty(m, dtype=torch.int32, device="cuda"))
+        rc = L.pmp_dubins_batch(ctx, _lib.stream_ptr(), ctypes.byref(prm), m, s.data_ptr(), g.data_ptr(),
+                                o["word"].data_ptr(), o["tpq"].data_ptr(), o["cost"].data_ptr(), o["n_points"].data_ptr(),
+                                pc, _lib.ptr(o["points"]), o["status"].data_ptr())
+        _lib.check(ctx, rc, "pmp_dubins_batch")
+        return o
+
+    out = launch(s, g, point_cap)
+    if retry_overflow and n and not cost_only:
+        _retry_overflowed(torch, out, n, point_cap, 3, lambda redo, idx, pc: launch(s[idx].contiguous(), g[idx].contiguous(), pc))
+    return out
+
+
+def dubins_cost_matrix(starts, goals, step: float, max_curv: float):
+    """The Dubins steering metric between every start and every goal on pmp_dubins_cost_matrix: starts
+    [A, 3], goals [B, 3] poses (x, y, yaw in radians) -> dict of device tensors cost [A, B] f64 and word
+    [A, B] u8 of Dubins(step, max_curv).generation(starts[a], goals[b]) (curve_generation/dubins_curve.py:
+    253-273), without sampling; the A B pairs are decoded in the kernel."""
+    torch, L, ctx = _open()
+    s = _dev(torch, starts, torch.float64).reshape(-1, 3)
+    g = _dev(torch, goals, torch.float64).reshape(-1, 3)
+    A, B = int(s.shape[0]), int(g.shape[0])
+    prm = _lib.DubinsParams(float(step), float(max_curv))
+    out = dict(cost=torch.empty((A, B), dtype=torch.float64, device="cuda"),
+               word=torch.empty((A, B), dtype=torch.uint8, device="cuda"))
+    rc = L.pmp_dubins_cost_matrix(ctx, _lib.stream_ptr(), ctypes.byref(prm), A, s.data_ptr(), B, g.data_ptr(),
+                                  out["cost"].data_ptr(), out["word"].data_ptr())
+    _lib.check(ctx, rc, "pmp_dubins_cost_matrix")
+    return out

@@ -1,5 +1,6 @@
-"""Name registries: drop-in SearchFactory (utils/planner/search_factory.py:13-51) and ControlFactory
-(utils/planner/control_factory.py:13-27) for the planners this package accelerates.  Names of
+"""Name registries: drop-in SearchFactory (utils/planner/search_factory.py:13-51), ControlFactory
+(utils/planner/control_factory.py:13-27) and CurveFactory (utils/planner/curve_factory.py:9-29) for the
+planners and curves this package accelerates.  Names of
 reference planners outside the accelerated hot path raise NotImplementedError (not silently
 substituted)."""
 from __future__ import annotations
@@ -43,3 +44,18 @@ class ControlFactory(object):
             raise NotImplementedError(f"{planner_name} is not a ControlFactory name of python_motion_planning_amd; "
                                       f"construct python_motion_planning_amd.{planner_name.upper()} directly")
         raise ValueError("The `planner_name` must be set correctly.")
+
+
+# the reference's curve names (utils/planner/curve_factory.py:14-27) with no kernel here
+_CURVE_OUT_OF_SCOPE = {"bezier", "polynomial", "reeds_shepp", "cubic_spline", "bspline", "fem_pos_smoother"}
+
+
+class CurveFactory(object):
+    def __call__(self, curve_name, **config):
+        from . import curve
+
+        if curve_name == "dubins":
+            return curve.Dubins(**config)
+        if curve_name in _CURVE_OUT_OF_SCOPE:
+            raise NotImplementedError(f"{curve_name} is outside the accelerated hot path of python_motion_planning_amd")
+        raise ValueError("The `curve_name` must be set correctly.")
