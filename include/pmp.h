@@ -776,6 +776,62 @@ int pmp_dubins_batch(pmp_ctx* ctx, void* stream, const pmp_dubins_params* prm, i
 int pmp_dubins_cost_matrix(pmp_ctx* ctx, void* stream, const pmp_dubins_params* prm, int A, const double* start_xyyaw,
                            int B, const double* goal_xyyaw, double* cost, uint8_t* word);
 
+/* ReedsShepp(step, max_curv) (curve_generation/reeds_shepp.py:30-32) */
+typedef struct {
+    double step;
+    double max_curv;
+} pmp_reeds_shepp_params;
+
+/*
+ * Batched Reeds-Shepp curves (curve_generation/reeds_shepp.py: the car that can reverse; the steering
+ * function of the nonholonomic sampling planners for parking-style manoeuvres).  Replaces
+ * ReedsShepp(step, max_curv).generation(start, goal) (:606-674) for n pose pairs: the frame x, y, phi
+ * (:621-627; phi = gyaw - syaw unwrapped), the 46 candidates of SCS, CCC, CSC, CCCC, CCSC, CCSCC (:235-573)
+ * in the reference's order, called slots 0..45 (0-1 SCS, 2-9 CCC, 10-17 CSC, 18-25 CCCC, 26-41 CCSC, 42-45
+ * CCSCC), each from the reference's primitive with its feasibility tests, its lengths as Path(lengths=...)
+ * writes them, path_length = sum(|l|) as Python's sum adds it, the first strictly shortest slot (:633-637),
+ * the interpolation loop (:646-657: per piece the repeated sum length += d_length with d_length of the
+ * length's sign, not k step; then the piece's exact end) from the local pose (0, 0, 0), the strip of trailing
+ * points whose local x is exactly 0.0 (:664-667: real points too, so equal poses return cost 0 and no
+ * point), the transformation back and pi2pi on the yaw (:670-672).  Slots and counts follow the
+ * reference's except where two slots tie to rounding (the mirrored CCC words have the same length
+ * mathematically, so ties are common); values match it to rounding.
+ *   start_xyyaw, goal_xyyaw [n][3] f64: x, y, yaw in radians
+ *   slot [n] u8      0..45; 255 = none
+ *   lengths [n][5]   the slot's signed piece lengths, curvature-normalised; NaN beyond the word's 3-5 pieces
+ *                    (all NaN with slot 255)
+ *   cost [n]         best_cost / max_curv, as generation() returns it (:674): in the units of x and y, where
+ *                    pmp_dubins_batch's cost is curvature-normalised as Dubins.generation() returns it; inf
+ *                    with slot 255
+ *   slot_costs [n][46] nullable: every candidate's path_length (curvature-normalised), NaN = infeasible: the
+ *                    k best manoeuvres without a second launch; NULL = not written
+ *   n_points [n]     the reference's len(x_list)
+ *   points [n][point_cap][3] nullable: x, y, yaw of the first min(n_points, point_cap) points; NULL =
+ *       costs and counts only (point_cap then only sizes the table of step sums)
+ *   status [n]  0 ok, 2 point_cap too small (the count is still reported and the first point_cap rows
+ *               are valid; a pair of more than 2^24 steps reports count 0), 4 the reference raises (a
+ *               non-finite pose leaves no candidate below inf and int(inf / step) is an OverflowError, or
+ *               the points overrun its int(cost / step) + pieces + 3 list slots: IndexError) or, a
+ *               documented limit, |syaw| > 64 or |gyaw - syaw| > 64 radians: the reference's M() spends
+ *               |phi| / 2 pi loop rounds there and never ends from about 1e16 on
+ * Refused with PMP_EINVAL (the reference never leaves its loop, or divides by zero): step <= 0 or
+ * non-finite, max_curv <= 0 or non-finite; null pointers; n < 0; point_cap < 1.
+ */
+int pmp_reeds_shepp_batch(pmp_ctx* ctx, void* stream, const pmp_reeds_shepp_params* prm, int n,
+                          const double* start_xyyaw, const double* goal_xyyaw, uint8_t* slot, double* lengths,
+                          double* cost, double* slot_costs, int32_t* n_points, int point_cap, double* points,
+                          int32_t* status);
+/*
+ * The Reeds-Shepp steering metric between every start and every goal: cost [A][B] (best_cost / max_curv)
+ * and slot [A][B] of generation(starts[a], goals[b]) (:621-637) as pmp_reeds_shepp_batch computes them,
+ * without sampling.  The pair index is decoded in the kernel; the A B pose pairs are never stored.  cost
+ * inf / slot 255 where the reference raises or the 64-radian limit refuses.  Refused with PMP_EINVAL as
+ * pmp_reeds_shepp_batch (step is checked although unused); A < 0 or B < 0.
+ */
+int pmp_reeds_shepp_cost_matrix(pmp_ctx* ctx, void* stream, const pmp_reeds_shepp_params* prm, int A,
+                                const double* start_xyyaw, int B, const double* goal_xyyaw, double* cost,
+                                uint8_t* slot);
+
 /* Launch-span recording for profiling: while set, every A* 2D launch of this context folds its
  * workers' first start and last end wall-clock ticks into span[0] (atomic min) and span[1] (atomic
  * max); the caller initialises span to {UINT64_MAX, 0}.  NULL switches it off. */

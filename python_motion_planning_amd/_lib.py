@@ -87,6 +87,8 @@ SIGNATURES = {
     "pmp_splinetraj3d_max_waypoints": (_i, []),
     "pmp_dubins_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "pmp_dubins_cost_matrix": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "pmp_reeds_shepp_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "pmp_reeds_shepp_cost_matrix": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
 }
 
 
@@ -200,6 +202,23 @@ class DubinsParams(ctypes.Structure):
 
 
 DUBINS_WORDS = ("LSL", "RSR", "LSR", "RSL", "RLR", "LRL")  # word 0..5, the reference's order (:264)
+
+
+class ReedsSheppParams(ctypes.Structure):
+    """pmp_reeds_shepp_params == ReedsShepp(step, max_curv) (curve_generation/reeds_shepp.py:30-32)."""
+    _fields_ = [("step", ctypes.c_double), ("max_curv", ctypes.c_double)]
+
+
+# slot 0..45: the ctypes of each Path(...) in the reference's order (reeds_shepp.py:235-573)
+RS_WORDS = (
+    "SLS", "SRS",                                                          # SCS
+    "LRL", "LRL", "RLR", "RLR", "LRL", "LRL", "RLR", "RLR",                # CCC, then CCC backwards
+    "LSL", "LSL", "RSR", "RSR", "LSR", "LSR", "RSL", "RSL",                # CSC
+    "LRLR", "LRLR", "RLRL", "RLRL", "LRLR", "LRLR", "RLRL", "RLRL",        # CCCC
+    "LRSL", "LRSL", "RLSR", "RLSR", "LRSR", "LRSR", "RLSL", "RLSL",        # CCSC
+    "LSRL", "LSRL", "RSLR", "RSLR", "RSRL", "RSRL", "LSLR", "LSLR",        # CCSC backwards
+    "LRSLR", "LRSLR", "RLSRL", "RLSRL",                                    # CCSCC
+)
 
 TRACK_LQR, TRACK_MPC = 0, 1
 

@@ -1126,3 +1126,78 @@ def dubins_cost_matrix(starts, goals, step: float, max_curv: float):
                                   out["cost"].data_ptr(), out["word"].data_ptr())
     _lib.check(ctx, rc, "pmp_dubins_cost_matrix")
     return out
+
+
+def _reeds_shepp_point_cap(torch, s, g, step, max_curv):
+    """An upper bound of a launch's point counts.  Every candidate but SLS is at most hypot max_curv + 2 of
+    straight piece (the circle centres are within 2 of the chord) and three arcs of at most pi each
+    (M()'s range; the pi / 2 arcs and CCCC's acos arcs are shorter), so the shortest is within hypot
+    max_curv + 4 pi wherever one of them is feasible; over the step, plus the reference's own 5 + 3 list
+    slots.  Pairs beyond it (only SLS feasible) are retried; pairs of non-finite poses or of more than
+    2^24 steps have no points; 2048 where the parameters give no bound."""
+    if not int(s.shape[0]):
+        return 1
+    if not (step > 0 and max_curv > 0 and math.isfinite(step) and math.isfinite(max_curv)):
+        return 2048  # the entry refuses these
+    est = (torch.hypot(g[:, 0] - s[:, 0], g[:, 1] - s[:, 1]) * max_curv + 4.0 * math.pi) / step + 8.0
+    return int(torch.where(est < float(1 << 24), est, torch.ones_like(est)).max().item())
+
+
+def reeds_shepp_batch(starts, goals, step: float, max_curv: float, cost_only: bool = False, point_cap: int | None = None,
+                      retry_overflow: bool = True, slot_costs: bool = False):
+    """Batched ReedsShepp(step, max_curv).generation(start, goal) (curve_generation/reeds_shepp.py:606-674)
+    on pmp_reeds_shepp_batch.  starts, goals: [n, 3] poses (x, y, yaw in radians), host arrays or device
+    tensors.  Returns dict of device tensors: slot [n] u8 (_lib.RS_WORDS; 255 = none), lengths [n, 5] (signed,
+    curvature-normalised, NaN beyond the word's pieces), cost [n] (best_cost / max_curv, as the reference
+    returns it), n_points [n], points [n, point_cap, 3] (x, y, yaw; None with cost_only), status
+    (include/pmp.h), and with slot_costs=True slot_costs [n, 46]: every candidate's path_length, NaN =
+    infeasible.  Pairs whose points overflow the first cap are re-run with their exact count when
+    retry_overflow."""
+    torch, L, ctx = _open()
+    s, g, n = _endpoints(torch, starts, goals, 3, torch.float64)
+    if int(g.shape[0]) != n:
+        raise ValueError("starts and goals must have the same length")
+    prm = _lib.ReedsSheppParams(float(step), float(max_curv))
+    if point_cap is None:
+        point_cap = _reeds_shepp_point_cap(torch, s, g, prm.step, prm.max_curv)
+    point_cap = max(int(point_cap), 1)
+
+    def launch(s, g, pc, with_costs=slot_costs):
+        m = int(s.shape[0])
+        f64 = dict(dtype=torch.float64, device="cuda")
+        o = dict(slot=torch.empty(m, dtype=torch.uint8, device="cuda"), lengths=torch.empty((m, 5), **f64),
+                 cost=torch.empty(m, **f64), n_points=torch.empty(m, dtype=torch.int32, device="cuda"),
+                 points=None if cost_only else torch.empty((m, pc, 3), **f64),
+                 status=torch.empty(m, dtype=torch.int32, device="cuda"))
+        if with_costs:
+            o["slot_costs"] = torch.empty((m, len(_lib.RS_WORDS)), **f64)
+        rc = L.pmp_reeds_shepp_batch(ctx, _lib.stream_ptr(), ctypes.byref(prm), m, s.data_ptr(), g.data_ptr(),
+                                     o["slot"].data_ptr(), o["lengths"].data_ptr(), o["cost"].data_ptr(),
+                                     _lib.ptr(o.get("slot_costs")), o["n_points"].data_ptr(), pc, _lib.ptr(o["points"]),
+                                     o["status"].data_ptr())
+        _lib.check(ctx, rc, "pmp_reeds_shepp_batch")
+        return o
+
+    out = launch(s, g, point_cap)
+    if retry_overflow and n and not cost_only:
+        _retry_overflowed(torch, out, n, point_cap, 3,
+                          lambda redo, idx, pc: launch(s[idx].contiguous(), g[idx].contiguous(), pc, False))
+    return out
+
+
+def reeds_shepp_cost_matrix(starts, goals, step: float, max_curv: float):
+    """The Reeds-Shepp steering metric between every start and every goal on pmp_reeds_shepp_cost_matrix:
+    starts [A, 3], goals [B, 3] poses (x, y, yaw in radians) -> dict of device tensors cost [A, B] f64
+    (best_cost / max_curv) and slot [A, B] u8 of ReedsShepp(step, max_curv).generation(starts[a], goals[b])
+    (curve_generation/reeds_shepp.py:621-637), without sampling; the A B pairs are decoded in the kernel."""
+    torch, L, ctx = _open()
+    s = _dev(torch, starts, torch.float64).reshape(-1, 3)
+    g = _dev(torch, goals, torch.float64).reshape(-1, 3)
+    A, B = int(s.shape[0]), int(g.shape[0])
+    prm = _lib.ReedsSheppParams(float(step), float(max_curv))
+    out = dict(cost=torch.empty((A, B), dtype=torch.float64, device="cuda"),
+               slot=torch.empty((A, B), dtype=torch.uint8, device="cuda"))
+    rc = L.pmp_reeds_shepp_cost_matrix(ctx, _lib.stream_ptr(), ctypes.byref(prm), A, s.data_ptr(), B, g.data_ptr(),
+                                       out["cost"].data_ptr(), out["slot"].data_ptr())
+    _lib.check(ctx, rc, "pmp_reeds_shepp_cost_matrix")
+    return out

@@ -15,11 +15,13 @@
 //     length at its end; pieces 2.. start where the previous piece ends, computed once per wave.  Rotation by
 //     theta, translation, pi2pi on the yaw; the rows (x, y, yaw) go through an LDS stage so that the
 //     wave stores them as one contiguous run.
-// The sampler takes a list of (mode, signed length) pieces, as the reference's loop does (d_length
-// follows the length's sign): another word family (Reeds-Shepp) needs a solver only.
+// The sampler (the steps kernel, interpolate, the pieces and their points, the strip) takes a list of
+// (mode, signed length) pieces, as the reference's loop does (d_length follows the length's sign); it
+// lives in curve_sample.h, instantiated here at three pieces, and reeds_shepp.hip shares it.
 #include <cmath>
 #include "localplan.h"
 #include "traj_sample.h"
+#include "curve_sample.h"
 
 namespace {
 
@@ -32,7 +34,6 @@ constexpr double kMaxAngle = 64.0;        // |theta|, |alpha|, |beta| beyond thi
 constexpr double kPi = lp::kPi;
 constexpr double kInf = __builtin_huge_val();
 
-enum { MODE_L = 0, MODE_S = 1, MODE_R = 2 };
 // the three modes of word w (LSL, RSR, LSR, RSL, RLR, LRL), two bits each, six bits a word
 constexpr uint64_t word_code(int a, int b, int c) { return (uint64_t)(a | (b << 2) | (c << 4)); }
 constexpr uint64_t kWordModes = word_code(MODE_L, MODE_S, MODE_L) | word_code(MODE_R, MODE_S, MODE_R) << 6 |
@@ -127,128 +128,7 @@ __device__ __forceinline__ dubins_best solve_words(const dubins_frame& f)
     return b;
 }
 
-struct pose {
-    double x, y, yaw;
-};
-// Dubins.interpolate (:207-236).  R is L with the length negated: x -+ and y +- of the same differences.
-__device__ __forceinline__ pose interpolate(int mode, double length, const pose& a, double max_curv)
-{
-    pose o;
-    if (mode == MODE_S) {
-        o.x = a.x + length / max_curv * cos(a.yaw);
-        o.y = a.y + length / max_curv * sin(a.yaw);
-        o.yaw = a.yaw;
-    } else {
-        const double yaw2 = mode == MODE_L ? a.yaw + length : a.yaw - length;
-        const double ds = (sin(yaw2) - sin(a.yaw)) / max_curv, dc = (cos(yaw2) - cos(a.yaw)) / max_curv;
-        o.x = mode == MODE_L ? a.x + ds : a.x - ds;
-        o.y = mode == MODE_L ? a.y - dc : a.y + dc;
-        o.yaw = yaw2;
-    }
-    return o;
-}
-
-// How many steps the reference's loop `length = d; while |length| <= |seg|: length += d` (:288-292) takes:
-// the k >= 1 with R[k] <= |seg|, R [nr] the repeated sums (R[0] = 0).  A piece longer than the table is
-// finished by the same additions.
-__device__ __forceinline__ int piece_steps(const double* __restrict__ R, int nr, double step, double seg)
-{
-    const double a = fabs(seg);
-    int lo = 1, hi = nr;  // the first k in [1, nr] with !(R[k] <= a)
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (R[mid] <= a) lo = mid + 1;
-        else hi = mid;
-    }
-    int k = lo - 1;
-    if (lo == nr && nr >= 1) {
-        double len = R[nr - 1] + step, prev = R[nr - 1];
-        while (len <= a && len > prev && k < 0x3fffffff) {
-            k++;
-            prev = len;
-            len += step;
-        }
-    }
-    return k;
-}
-
-// A curve as the sampler sees it: np pieces of (mode, signed length), their step counts and start poses
-struct dubins_pieces {
-    int mode[kMaxPieces];
-    double len[kMaxPieces];
-    int cnt[kMaxPieces];
-    pose start[kMaxPieces];
-    pose end;  // of the last piece
-    int total;  // 1 + sum(cnt + 1): the points the reference writes
-};
-
-__device__ __forceinline__ void lay_pieces(dubins_pieces& P, int np, double alpha, const double* __restrict__ R, int nr,
-                                           double step, double max_curv)
-{
-    pose cur = {0.0, 0.0, alpha};
-    int total = 1;
-#pragma unroll
-    for (int j = 0; j < kMaxPieces; j++) {
-        if (j < np) {
-            P.cnt[j] = piece_steps(R, nr, step, P.len[j]);
-            P.start[j] = cur;
-            cur = interpolate(P.mode[j], P.len[j], cur, max_curv);
-            total += P.cnt[j] + 1;
-        }
-    }
-    P.end = cur;
-    P.total = total;
-}
-
-// R[k] of the table, or the same additions carried on past its end (k >= nr: only a piece longer than
-// every buffer of the launch, and only when the strip below reaches into it)
-__device__ __forceinline__ double step_sum(const double* __restrict__ R, int nr, double step, int k)
-{
-    if (k < nr) return R[k];
-    double acc = R[nr - 1];
-    for (int m = nr - 1; m < k; m++) acc += step;
-    return acc;
-}
-
-// Point i (0 <= i < total) in the local frame: the start, or piece j's k-th step / its end
-__device__ __forceinline__ pose local_point(const dubins_pieces& P, int np, int i, double alpha,
-                                            const double* __restrict__ R, int nr, double step, double max_curv)
-{
-    if (i == 0) return pose{0.0, 0.0, alpha};
-    int base = 0;
-    pose o = P.end;
-#pragma unroll
-    for (int j = 0; j < kMaxPieces; j++) {
-        if (j < np) {
-            const int k = i - base;  // 1 .. cnt: a step; cnt + 1: the piece's end
-            if (k >= 1 && k <= P.cnt[j]) {
-                const double r = step_sum(R, nr, step, k);
-                const double l = P.len[j] > 0.0 ? r : -r;
-                o = interpolate(P.mode[j], l, P.start[j], max_curv);
-            } else if (k == P.cnt[j] + 1 && j + 1 < np) {
-                o = P.start[j + 1];
-            }
-            base += P.cnt[j] + 1;
-        }
-    }
-    return o;
-}
-
-// The reference's count: total less the trailing points whose local x is exactly 0.0 (:301-304; its unused
-// slots are 0.0 too, so the strip runs on into the real points)
-__device__ __forceinline__ int stripped_count(const dubins_pieces& P, int np, double alpha, const double* __restrict__ R,
-                                              int nr, double step, double max_curv)
-{
-    int n = P.total;
-    while (n >= 1) {
-        const pose o = local_point(P, np, n - 1, alpha, R, nr, step, max_curv);
-        if (!(o.x == 0.0)) break;
-        n--;
-    }
-    return n;
-}
-
-__device__ __forceinline__ void word_pieces(dubins_pieces& P, int word, double t, double p, double q)
+__device__ __forceinline__ void word_pieces(curve_pieces<kMaxPieces>& P, int word, double t, double p, double q)
 {
     P.mode[0] = word_mode(word, 0);
     P.mode[1] = word_mode(word, 1);
@@ -256,17 +136,6 @@ __device__ __forceinline__ void word_pieces(dubins_pieces& P, int word, double t
     P.len[0] = t;
     P.len[1] = p;
     P.len[2] = q;
-}
-
-// R[0] = 0, R[k + 1] = R[k] + step: one lane, the reference's own additions
-__global__ void dubins_steps_kernel(double step, int nr, double* __restrict__ R)
-{
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    double acc = 0.0;
-    for (int k = 0; k < nr; k++) {
-        R[k] = acc;
-        acc += step;
-    }
 }
 
 template <bool MATRIX>
@@ -305,7 +174,7 @@ __global__ __launch_bounds__(256) void dubins_solve_kernel(pmp_dubins_params C, 
         st_out[i] = PMP_PATH_OVERFLOW;
         return;
     }
-    dubins_pieces P;
+    curve_pieces<kMaxPieces> P;
     word_pieces(P, b.word, b.t, b.p, b.q);
     lay_pieces(P, 3, f.alpha, R, nr, C.step, C.max_curv);
     if ((double)P.total > trunc(slots) + 6.0) {
@@ -336,7 +205,7 @@ __global__ __launch_bounds__(64) void dubins_sample_kernel(pmp_dubins_params C, 
     const double s[3] = {starts[3 * (size_t)q], starts[3 * (size_t)q + 1], starts[3 * (size_t)q + 2]};
     const double g[3] = {goals[3 * (size_t)q], goals[3 * (size_t)q + 1], goals[3 * (size_t)q + 2]};
     const dubins_frame f = make_frame(s, g, C.max_curv);
-    dubins_pieces P;
+    curve_pieces<kMaxPieces> P;
     word_pieces(P, word, tpq_in[3 * (size_t)q], tpq_in[3 * (size_t)q + 1], tpq_in[3 * (size_t)q + 2]);
     lay_pieces(P, 3, f.alpha, R, nr, C.step, C.max_curv);
     const double ct = cos(f.theta), sn = sin(f.theta);
@@ -385,7 +254,7 @@ extern "C" int pmp_dubins_batch(pmp_ctx* ctx, void* stream, const pmp_dubins_par
     const int nr = (points ? point_cap : std::min(point_cap, kStepsCostOnly)) + 1;
     double* R = (double*)pmp_scratch(ctx, SCR_DUBINS_STEPS, (size_t)nr * 8);
     if (!R) return PMP_ENOMEM;
-    hipLaunchKernelGGL(dubins_steps_kernel, dim3(1), dim3(64), 0, s, prm->step, nr, R);
+    hipLaunchKernelGGL(curve_steps_kernel, dim3(1), dim3(64), 0, s, prm->step, nr, R);
     hipLaunchKernelGGL(dubins_solve_kernel<false>, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, s, *prm, (size_t)n, start_xyyaw,
                        goal_xyyaw, (size_t)1, R, nr, point_cap, points ? 1 : 0, word, tpq, cost, n_points, status);
     if (points)
