@@ -832,6 +832,86 @@ int pmp_reeds_shepp_cost_matrix(pmp_ctx* ctx, void* stream, const pmp_reeds_shep
                                 const double* start_xyyaw, int B, const double* goal_xyyaw, double* cost,
                                 uint8_t* slot);
 
+/* Polynomial(step, max_acc, max_jerk) and its instance attributes dt, t_min, t_max
+ * (curve_generation/polynomial_curve.py:28-34; the reference's defaults are 0.1, 1, 30) */
+typedef struct {
+    double step;
+    double max_acc;
+    double max_jerk;
+    double dt;
+    double t_min;
+    double t_max;
+} pmp_polycurve_params;
+
+/*
+ * Batched quintic polynomial curves (curve_generation/polynomial_curve.py): the minimum-time connection of
+ * two states (x, y, yaw, v, a) under peak-acceleration and peak-jerk limits, the steering function and time
+ * metric of a kinodynamic sampling planner.  Replaces Polynomial(step, max_acc, max_jerk).generation(start,
+ * goal) (:104-164) for n state pairs: the velocities and accelerations split by cos / sin of the yaws
+ * (:118-126), the candidate times T_i = np.arange(t_min, t_max, step)[i] = t_min + i ((t_min + step) - t_min),
+ * ceil((t_max - t_min) / step) of them (:130), per candidate and axis the 3 x 3 solve of Poly.__init__
+ * (:43-61; Gaussian elimination with partial pivoting, where the reference calls LAPACK), the sample times
+ * k dt, k < ceil((T + dt) / dt) (:134), and the first candidate with max hypot(ax, ay) <= max_acc and
+ * max hypot(jx, jy) <= max_jerk (:158-160; a NaN peak is infeasible).  The rows of that candidate are the
+ * reference's (:135-156): yaw = atan2(vy, vx), v = hypot(vx, vy), a = hypot(ax, ay) negated where
+ * v[k] - v[k-1] < 0, jerk = hypot(jx, jy) negated where the signed a[k] - a[k-1] < 0 (row 0 has neither rule).
+ * t_index and the counts follow the reference's unless a peak lies within rounding of its limit; values
+ * match it to rounding (the signs of a and jerk where the difference they turn on is not itself rounding).
+ *   start, goal [n][5] f64: x, y, yaw in radians, v, a
+ *   t_index [n] i32  the chosen candidate's index i; -1 = no candidate is feasible
+ *   T [n]            its time T_i; inf with t_index -1
+ *   n_points [n]     the reference's traj.size: ceil((T + dt) / dt); 0 with t_index -1
+ *   points [n][point_cap][7] nullable: time, x, y, yaw, v, a, jerk of the first min(n_points, point_cap) rows;
+ *       NULL = t_index, T and counts only (point_cap is then unused but must be >= 1)
+ *   status [n]  0 ok, 1 no feasible T (the reference returns an empty trajectory: also for a NaN or infinite
+ *               pose and for a goal too far to reach within t_max), 2 point_cap too small (the count is still
+ *               reported and the first point_cap rows are valid)
+ * Refused with PMP_EINVAL (the reference never ends, raises, or answers with garbage): step <= 0 or
+ * non-finite; dt <= 0 or non-finite; t_min <= 0 (the system is singular at T = 0) or non-finite; t_max
+ * non-finite; max_acc or max_jerk non-finite; more than 2^24 candidate times or sample times; null pointers;
+ * n < 0; point_cap < 1.  t_max <= t_min is no error: there is no candidate, status 1.
+ */
+int pmp_polycurve_batch(pmp_ctx* ctx, void* stream, const pmp_polycurve_params* prm, int n, const double* start,
+                        const double* goal, int32_t* t_index, double* T, int32_t* n_points, int point_cap,
+                        double* points, int32_t* status);
+/*
+ * The minimum-time metric between every start and every goal state: T [A][B] (inf where no candidate is
+ * feasible) and t_index [A][B] (-1 there) of generation(starts[a], goals[b]) as pmp_polycurve_batch finds
+ * them, without sampling.  The pair index is decoded in the kernel; the A B state pairs are never stored.
+ * start [A][5], goal [B][5].  Refused with PMP_EINVAL as pmp_polycurve_batch; A < 0 or B < 0.
+ */
+int pmp_polycurve_time_matrix(pmp_ctx* ctx, void* stream, const pmp_polycurve_params* prm, int A, const double* start,
+                              int B, const double* goal, double* T, int32_t* t_index);
+
+/* Bezier(step, offset) (curve_generation/bezier_curve.py:27-29) */
+typedef struct {
+    double step;
+    double offset;
+} pmp_bezier_params;
+
+/*
+ * Batched cubic Bezier curves (curve_generation/bezier_curve.py).  Replaces Bezier(step, offset).generation(
+ * start, goal) (:34-53) for n pose pairs: n_points = int(hypot(sx - gx, sy - gy) / step) (:49), the control
+ * points P0 = start, P1 = start + d (cos syaw, sin syaw), P2 = goal - d (cos gyaw, sin gyaw), P3 = goal with
+ * d = hypot / offset (:82-89), and the point at each t of np.linspace(0, 1, n_points) (t_i = i (1 / (n - 1)),
+ * the last exactly 1; a single point has t = 0) as the left-to-right sum over i = 0..3 of
+ * ((C(3, i) t^i) (1 - t)^(3 - i)) P_i (:66-69).  Counts follow the reference's unless hypot / step lies within
+ * rounding of an integer; values match it to rounding.
+ *   start_xyyaw, goal_xyyaw [n][3] f64: x, y, yaw in radians
+ *   control [n][4][2]  the control points
+ *   n_points [n]       the reference's len(path); poses closer than step have no point
+ *   points [n][point_cap][2] nullable: x, y of the first min(n_points, point_cap) points; NULL = counts and
+ *       control points only
+ *   status [n]  0 ok, 2 point_cap too small (the count is still reported and the first point_cap rows are
+ *               valid; a pair of more than 2^24 points reports count 0), 4 the reference raises (a non-finite
+ *               pose: int(nan) is a ValueError, int(inf) an OverflowError)
+ * Refused with PMP_EINVAL (the reference divides by zero or answers with NaN): step <= 0 or non-finite,
+ * offset == 0 or non-finite; null pointers; n < 0; point_cap < 1.
+ */
+int pmp_bezier_batch(pmp_ctx* ctx, void* stream, const pmp_bezier_params* prm, int n, const double* start_xyyaw,
+                     const double* goal_xyyaw, double* control, int32_t* n_points, int point_cap, double* points,
+                     int32_t* status);
+
 /* Launch-span recording for profiling: while set, every A* 2D launch of this context folds its
  * workers' first start and last end wall-clock ticks into span[0] (atomic min) and span[1] (atomic
  * max); the caller initialises span to {UINT64_MAX, 0}.  NULL switches it off. */

@@ -89,6 +89,9 @@ SIGNATURES = {
     "pmp_dubins_cost_matrix": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "pmp_reeds_shepp_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "pmp_reeds_shepp_cost_matrix": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "pmp_polycurve_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "pmp_polycurve_time_matrix": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "pmp_bezier_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
 }
 
 
@@ -219,6 +222,18 @@ RS_WORDS = (
     "LSRL", "LSRL", "RSLR", "RSLR", "RSRL", "RSRL", "LSLR", "LSLR",        # CCSC backwards
     "LRSLR", "LRSLR", "RLSRL", "RLSRL",                                    # CCSCC
 )
+
+
+class PolyCurveParams(ctypes.Structure):
+    """pmp_polycurve_params == Polynomial(step, max_acc, max_jerk) and its attributes dt, t_min, t_max
+    (curve_generation/polynomial_curve.py:28-34)."""
+    _fields_ = [(n, ctypes.c_double) for n in ("step", "max_acc", "max_jerk", "dt", "t_min", "t_max")]
+
+
+class BezierParams(ctypes.Structure):
+    """pmp_bezier_params == Bezier(step, offset) (curve_generation/bezier_curve.py:27-29)."""
+    _fields_ = [("step", ctypes.c_double), ("offset", ctypes.c_double)]
+
 
 TRACK_LQR, TRACK_MPC = 0, 1
 

@@ -1201,3 +1201,118 @@ def reeds_shepp_cost_matrix(starts, goals, step: float, max_curv: float):
                                        out["cost"].data_ptr(), out["slot"].data_ptr())
     _lib.check(ctx, rc, "pmp_reeds_shepp_cost_matrix")
     return out
+
+
+def _polycurve_params(step, max_acc, max_jerk, dt, t_min, t_max):
+    return _lib.PolyCurveParams(float(step), float(max_acc), float(max_jerk), float(dt), float(t_min), float(t_max))
+
+
+def _polycurve_point_cap(prm):
+    """The exact largest row count of a launch, ceil((t_max + dt) / dt): every candidate's time is below
+    t_max; 1 where the parameters give none (the entry refuses them)."""
+    if not (prm.dt > 0 and math.isfinite(prm.dt) and math.isfinite(prm.t_max)):
+        return 1
+    cap = math.ceil((prm.t_max + prm.dt) / prm.dt)
+    return int(cap) if 1 <= cap <= (1 << 24) else 1
+
+
+def polynomial_batch(starts, goals, step: float, max_acc: float, max_jerk: float, dt: float = 0.1, t_min: float = 1,
+                     t_max: float = 30, cost_only: bool = False, point_cap: int | None = None,
+                     retry_overflow: bool = True):
+    """Batched Polynomial(step, max_acc, max_jerk).generation(start, goal) (curve_generation/
+    polynomial_curve.py:104-164) on pmp_polycurve_batch.  starts, goals: [n, 5] states (x, y, yaw in radians,
+    v, a), host arrays or device tensors; dt, t_min, t_max are the reference's instance attributes.  Returns
+    dict of device tensors: t_index [n] i32 (-1 = no feasible T), T [n] (inf there), n_points [n], points
+    [n, point_cap, 7] (time, x, y, yaw, v, a, jerk; None with cost_only), status (include/pmp.h: 1 = no
+    feasible T).  Pairs whose rows overflow a caller's point_cap are re-run with their exact count when
+    retry_overflow; the default cap holds every candidate."""
+    torch, L, ctx = _open()
+    s, g, n = _endpoints(torch, starts, goals, 5, torch.float64)
+    if int(g.shape[0]) != n:
+        raise ValueError("starts and goals must have the same length")
+    prm = _polycurve_params(step, max_acc, max_jerk, dt, t_min, t_max)
+    if point_cap is None:
+        point_cap = _polycurve_point_cap(prm)
+    point_cap = max(int(point_cap), 1)
+
+    def launch(s, g, pc):
+        m = int(s.shape[0])
+        i32 = dict(dtype=torch.int32, device="cuda")
+        o = dict(t_index=torch.empty(m, **i32), T=torch.empty(m, dtype=torch.float64, device="cuda"),
+                 n_points=torch.empty(m, **i32),
+                 points=None if cost_only else torch.empty((m, pc, 7), dtype=torch.float64, device="cuda"),
+                 status=torch.empty(m, **i32))
+        rc = L.pmp_polycurve_batch(ctx, _lib.stream_ptr(), ctypes.byref(prm), m, s.data_ptr(), g.data_ptr(),
+                                   o["t_index"].data_ptr(), o["T"].data_ptr(), o["n_points"].data_ptr(), pc,
+                                   _lib.ptr(o["points"]), o["status"].data_ptr())
+        _lib.check(ctx, rc, "pmp_polycurve_batch")
+        return o
+
+    out = launch(s, g, point_cap)
+    if retry_overflow and n and not cost_only:
+        _retry_overflowed(torch, out, n, point_cap, 7, lambda redo, idx, pc: launch(s[idx].contiguous(), g[idx].contiguous(), pc))
+    return out
+
+
+def polynomial_time_matrix(starts, goals, step: float, max_acc: float, max_jerk: float, dt: float = 0.1,
+                           t_min: float = 1, t_max: float = 30):
+    """The minimum-time metric between every start and every goal state on pmp_polycurve_time_matrix: starts
+    [A, 5], goals [B, 5] states (x, y, yaw in radians, v, a) -> dict of device tensors T [A, B] f64 (inf where
+    no candidate is feasible) and t_index [A, B] i32 (-1 there) of Polynomial(step, max_acc,
+    max_jerk).generation(starts[a], goals[b]) (curve_generation/polynomial_curve.py:130-160), without
+    sampling; the A B pairs are decoded in the kernel."""
+    torch, L, ctx = _open()
+    s = _dev(torch, starts, torch.float64).reshape(-1, 5)
+    g = _dev(torch, goals, torch.float64).reshape(-1, 5)
+    A, B = int(s.shape[0]), int(g.shape[0])
+    prm = _polycurve_params(step, max_acc, max_jerk, dt, t_min, t_max)
+    out = dict(T=torch.empty((A, B), dtype=torch.float64, device="cuda"),
+               t_index=torch.empty((A, B), dtype=torch.int32, device="cuda"))
+    rc = L.pmp_polycurve_time_matrix(ctx, _lib.stream_ptr(), ctypes.byref(prm), A, s.data_ptr(), B, g.data_ptr(),
+                                     out["T"].data_ptr(), out["t_index"].data_ptr())
+    _lib.check(ctx, rc, "pmp_polycurve_time_matrix")
+    return out
+
+
+def _bezier_point_cap(torch, s, g, step):
+    """The largest int(hypot / step) of a launch (a pair whose count the device rounds one higher is
+    retried; pairs of non-finite poses or of more than 2^24 points have no points); 1 where the step gives
+    none (the entry refuses it)."""
+    if not int(s.shape[0]) or not (step > 0 and math.isfinite(step)):
+        return 1
+    est = torch.hypot(s[:, 0] - g[:, 0], s[:, 1] - g[:, 1]) / step
+    return max(int(torch.where(est < float(1 << 24), est, torch.ones_like(est)).max().item()), 1)
+
+
+def bezier_batch(starts, goals, step: float, offset: float, cost_only: bool = False, point_cap: int | None = None,
+                 retry_overflow: bool = True):
+    """Batched Bezier(step, offset).generation(start, goal) (curve_generation/bezier_curve.py:34-89) on
+    pmp_bezier_batch.  starts, goals: [n, 3] poses (x, y, yaw in radians), host arrays or device tensors.
+    Returns dict of device tensors: control [n, 4, 2], n_points [n], points [n, point_cap, 2] (x, y; None with
+    cost_only), status (include/pmp.h: 4 = a non-finite pose, where the reference raises).  Pairs whose
+    points overflow the first cap are re-run with their exact count when retry_overflow."""
+    torch, L, ctx = _open()
+    s, g, n = _endpoints(torch, starts, goals, 3, torch.float64)
+    if int(g.shape[0]) != n:
+        raise ValueError("starts and goals must have the same length")
+    prm = _lib.BezierParams(float(step), float(offset))
+    if point_cap is None:
+        point_cap = _bezier_point_cap(torch, s, g, prm.step)
+    point_cap = max(int(point_cap), 1)
+
+    def launch(s, g, pc):
+        m = int(s.shape[0])
+        f64 = dict(dtype=torch.float64, device="cuda")
+        o = dict(control=torch.empty((m, 4, 2), **f64), n_points=torch.empty(m, dtype=torch.int32, device="cuda"),
+                 points=None if cost_only else torch.empty((m, pc, 2), **f64),
+                 status=torch.empty(m, dtype=torch.int32, device="cuda"))
+        rc = L.pmp_bezier_batch(ctx, _lib.stream_ptr(), ctypes.byref(prm), m, s.data_ptr(), g.data_ptr(),
+                                o["control"].data_ptr(), o["n_points"].data_ptr(), pc, _lib.ptr(o["points"]),
+                                o["status"].data_ptr())
+        _lib.check(ctx, rc, "pmp_bezier_batch")
+        return o
+
+    out = launch(s, g, point_cap)
+    if retry_overflow and n and not cost_only:
+        _retry_overflowed(torch, out, n, point_cap, 2, lambda redo, idx, pc: launch(s[idx].contiguous(), g[idx].contiguous(), pc))
+    return out

@@ -3,13 +3,16 @@
   Curve    curve_generation/curve.py:10-64         the base: step, trigonometric, pi2pi, mod2pi, length
   Dubins   curve_generation/dubins_curve.py:14-335 pmp_dubins_batch / pmp_dubins_cost_matrix
   ReedsShepp curve_generation/reeds_shepp.py:13-736 pmp_reeds_shepp_batch / pmp_reeds_shepp_cost_matrix
+  Polynomial curve_generation/polynomial_curve.py:13-195 pmp_polycurve_batch / pmp_polycurve_time_matrix
+  Bezier   curve_generation/bezier_curve.py:13-111 pmp_bezier_batch
 
 Same constructor, generation() return values and run() input (yaw in degrees) as the reference; run() does
 not plot (as Planner.run, planner.py:31-33).  Many pose pairs at once: generation_batch and cost_matrix of
 either class, or batch.dubins_batch / batch.dubins_cost_matrix and batch.reeds_shepp_batch /
 batch.reeds_shepp_cost_matrix.  Dubins.generation() returns its cost in curvature-normalised units and
-ReedsShepp.generation() in the units of x and y, as the reference's do.  CurveFactory builds "dubins" only:
-construct ReedsShepp directly.  There is no CPU fallback: without the library or a HIP device the calls
+ReedsShepp.generation() in the units of x and y, as the reference's do.  Polynomial takes 5-tuples (x, y,
+yaw, v, a) and has generation_batch and time_matrix; Bezier has generation_batch.  CurveFactory builds
+"dubins" only: construct ReedsShepp, Polynomial and Bezier directly.  There is no CPU fallback: without the library or a HIP device the calls
 raise PMPError.
 """
 from __future__ import annotations
@@ -195,3 +198,165 @@ class ReedsShepp(Curve):
             path_y.extend(y.tolist())
             path_yaw.extend(yaw)
         return path_x, path_y, path_yaw
+
+
+class Polynomial(Curve):
+    """Quintic polynomial curve generation (polynomial_curve.py:13-195): the first T of
+    np.arange(t_min, t_max, step) whose trajectory keeps its peak acceleration and jerk under the limits.
+
+    Parameters:
+        step (float): The spacing of the candidate times T
+        max_acc (float): Maximum acceleration
+        max_jerk (float): Maximum jerk
+
+    dt, t_min and t_max are instance attributes as in the reference (0.1, 1, 30), read at call time.  The
+    reference's Poly class (the 3 x 3 boundary-value solve and its x / dx / ddx / dddx) is the kernel's and is
+    not a class here.
+    """
+
+    def __init__(self, step: float, max_acc: float, max_jerk: float) -> None:
+        super().__init__(step)
+        self.max_acc = max_acc
+        self.max_jerk = max_jerk
+        self.dt = 0.1
+        self.t_min = 1
+        self.t_max = 30
+
+    def __str__(self) -> str:
+        return "Quintic Polynomial Curve"
+
+    class Trajectory:
+        """time, x, y, yaw, v, a, jerk as lists of floats (polynomial_curve.py:77-102)"""
+
+        def __init__(self):
+            self.clear()
+
+        def clear(self):
+            self.time = []
+            self.x = []
+            self.y = []
+            self.yaw = []
+            self.v = []
+            self.a = []
+            self.jerk = []
+
+        @property
+        def size(self):
+            assert len(self.time) == len(self.x) and \
+                   len(self.x) == len(self.y) and    \
+                   len(self.y) == len(self.yaw) and  \
+                   len(self.yaw) == len(self.v) and  \
+                   len(self.v) == len(self.a) and    \
+                   len(self.a) == len(self.jerk),    \
+                   "Unequal dimensions of each attribute, this should not happen."
+            return len(self.time)
+
+    def _params(self):
+        return dict(step=self.step, max_acc=self.max_acc, max_jerk=self.max_jerk, dt=self.dt, t_min=self.t_min,
+                    t_max=self.t_max)
+
+    def generation_batch(self, start_states, goal_states, **kw):
+        """batch.polynomial_batch with this generator's parameters (states x, y, yaw in radians, v, a)."""
+        return batch.polynomial_batch(start_states, goal_states, **self._params(), **kw)
+
+    def time_matrix(self, start_states, goal_states):
+        """batch.polynomial_time_matrix with this generator's parameters."""
+        return batch.polynomial_time_matrix(start_states, goal_states, **self._params())
+
+    def _segments(self, starts, goals):
+        """One launch -> a Trajectory per pair, empty where no T is feasible."""
+        r = self.generation_batch(starts, goals)
+        npt, pts = r["n_points"].cpu().numpy(), r["points"].cpu().numpy()
+        out = []
+        for i in range(len(npt)):
+            traj = self.Trajectory()
+            p = pts[i, : npt[i]]
+            for c, name in enumerate(("time", "x", "y", "yaw", "v", "a", "jerk")):
+                setattr(traj, name, p[:, c].tolist())
+            out.append(traj)
+        return out
+
+    def generation(self, start_pose: tuple, goal_pose: tuple):
+        """The first trajectory that satisfies the acceleration and jerk constraints (:104-164), from
+        start_pose to goal_pose (x, y, yaw in radians, v, a); an empty Trajectory where none does."""
+        return self._segments([tuple(start_pose)], [tuple(goal_pose)])[0]
+
+    def run(self, points: list):
+        """The curve through `points` [(x, y, yaw in degrees)] (:166-195) with the reference's heuristic
+        speeds (0, then 1) and accelerations: every segment in one launch, concatenated.  Returns (path_x,
+        path_y, path_yaw); nothing is plotted."""
+        assert len(points) >= 2, "Number of points should be at least 2."
+        v = [0]
+        for i in range(len(points) - 1):
+            v.append(1.0)
+        a = [(v[i + 1] - v[i]) / 5 for i in range(len(points) - 1)]
+        a.append(0)
+        states = [(p[0], p[1], np.deg2rad(p[2]), v[i], a[i]) for i, p in enumerate(points)]
+        path_x, path_y, path_yaw = [], [], []
+        for traj in self._segments(states[:-1], states[1:]):
+            path_x.extend(traj.x)
+            path_y.extend(traj.y)
+            path_yaw.extend(traj.yaw)
+        return path_x, path_y, path_yaw
+
+
+class Bezier(Curve):
+    """Bezier curve generation (bezier_curve.py:13-111).
+
+    Parameters:
+        step (float): Simulation or interpolation size
+        offset (float): The offset of control points
+    """
+
+    def __init__(self, step: float, offset: float) -> None:
+        super().__init__(step)
+        self.offset = offset
+
+    def __str__(self) -> str:
+        return "Bezier Curve"
+
+    def generation_batch(self, start_poses, goal_poses, **kw):
+        """batch.bezier_batch with this generator's step and offset (yaw in radians)."""
+        return batch.bezier_batch(start_poses, goal_poses, self.step, self.offset, **kw)
+
+    def _segments(self, starts, goals):
+        """One launch -> per pair (points, control_points) as generation() returns them."""
+        r = self.generation_batch(starts, goals)
+        st = r["status"].cpu().numpy()
+        for i in np.nonzero(st == _lib.STATUS_REF_RAISES)[0]:  # int() of hypot / step (:49)
+            if any(math.isnan(float(v)) for v in tuple(starts[i])[:2] + tuple(goals[i])[:2]):
+                raise ValueError("cannot convert float NaN to integer")
+            raise OverflowError("cannot convert float infinity to integer")
+        npt, pts, ctrl = r["n_points"].cpu().numpy(), r["points"].cpu().numpy(), r["control"].cpu().numpy()
+        return [([pts[i, k].copy() for k in range(npt[i])], [(c[0], c[1]) for c in ctrl[i]]) for i in range(len(st))]
+
+    def generation(self, start_pose: tuple, goal_pose: tuple):
+        """(points, control_points) of bezier_curve.py:34-53: the int(hypot / step) points as arrays of
+        shape (2,), the four control points as (x, y) tuples."""
+        return self._segments([tuple(start_pose)], [tuple(goal_pose)])[0]
+
+    def bezier(self, t: float, control_points: list) -> np.ndarray:
+        """The point at t of the Bezier curve of any number of control points (:55-69), on the host."""
+        n = len(control_points) - 1
+        control_points = np.array(control_points)
+        return np.sum([math.comb(n, i) * t ** i * (1 - t) ** (n - i) * control_points[i] for i in range(n + 1)], axis=0)
+
+    def getControlPoints(self, start_pose: tuple, goal_pose: tuple):
+        """The four control points of a pose pair (:71-89), on the host."""
+        sx, sy, syaw = start_pose
+        gx, gy, gyaw = goal_pose
+        dist = np.hypot(sx - gx, sy - gy) / self.offset
+        return [(sx, sy), (sx + dist * np.cos(syaw), sy + dist * np.sin(syaw)),
+                (gx - dist * np.cos(gyaw), gy - dist * np.sin(gyaw)), (gx, gy)]
+
+    def run(self, points: list):
+        """The curve through `points` [(x, y, yaw in degrees)] (:91-111): every segment in one launch,
+        concatenated.  Returns (path_x, path_y); nothing is plotted."""
+        assert len(points) >= 2, "Number of points should be at least 2."
+        poses = [(p[0], p[1], np.deg2rad(p[2])) for p in points]
+        path_x, path_y = [], []
+        for path, _ in self._segments(poses[:-1], poses[1:]):
+            for pt in path:
+                path_x.append(pt[0])
+                path_y.append(pt[1])
+        return path_x, path_y

@@ -46,9 +46,10 @@ class ControlFactory(object):
         raise ValueError("The `planner_name` must be set correctly.")
 
 
-# the reference's curve names (utils/planner/curve_factory.py:14-27) the factory refuses: five with no kernel
-# here, and "reeds_shepp", which has one (curve.ReedsShepp, csrc/reeds_shepp.hip) but keeps its refusal as
-# "jps", "rrt_connect" and "pid" do in their factories: construct the class
+# the reference's curve names (utils/planner/curve_factory.py:14-27) the factory refuses: three with no kernel
+# here, and "reeds_shepp", "polynomial" and "bezier", which have one (curve.ReedsShepp, csrc/reeds_shepp.hip;
+# curve.Polynomial and curve.Bezier, csrc/polycurve.hip) but keep their refusal as "jps", "rrt_connect" and
+# "pid" do in their factories: construct the class
 _CURVE_OUT_OF_SCOPE = {"bezier", "polynomial", "reeds_shepp", "cubic_spline", "bspline", "fem_pos_smoother"}
 
 

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""Pairs/s, segments/s, points/s and store bandwidth of the curve kernels (dubins.hip, reeds_shepp.hip).
+"""Pairs/s, segments/s, points/s and store bandwidth of the curve kernels (dubins.hip, reeds_shepp.hip,
+polycurve.hip).
 
-    python tools/curve_rate.py --kind dubins|reeds_shepp [--matrix 1024] [--segments 65536] [--warmup 3] [--repeats 9]
+    python tools/curve_rate.py --kind dubins|reeds_shepp|polynomial|bezier [--matrix 1024] [--segments 65536] [--warmup 3] [--repeats 9]
                                [--out FILE] [--reference-src DIR [--reference-pairs 200]]
 
 Poses are default_rng(0): x, y in 0..40, yaw in -pi..pi; step 0.1, max_curv 0.25
 (examples/curve_examples.py:27).  Per repeat, between two device events each:
-(dubins shown; reeds_shepp: batch.reeds_shepp_*, pmp_reeds_shepp_batch without slot_costs, ReedsShepp)
+(dubins shown; reeds_shepp: batch.reeds_shepp_*, pmp_reeds_shepp_batch without slot_costs, ReedsShepp;
+polynomial: states with v in 0..2 and a in -0.3..0.3, step 0.1, max_acc 1.0, max_jerk 0.5, batch.polynomial_batch /
+polynomial_time_matrix, pmp_polycurve_batch, 56 B a row, Polynomial; bezier: step 0.1, offset 3.0,
+batch.bezier_batch, pmp_bezier_batch, 16 B a row, Bezier, no matrix leg)
   cost_matrix   batch.dubins_cost_matrix of --matrix x --matrix poses (1024: 1.05M pairs): pairs/s
   kernel        pmp_dubins_batch alone on --segments pairs, buffers allocated once: segments/s, points/s and
                 the bytes of point rows stored (24 B a point) per second as a share of the 8 TB/s HBM peak
@@ -31,12 +35,22 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 STEP, CURV = 0.1, 0.25
+POLY = (0.1, 1.0, 0.5)  # step, max_acc, max_jerk; dt, t_min, t_max are the reference's 0.1, 1, 30
+BEZIER = (0.1, 3.0)     # step, offset
 HBM_PEAK = 8.0e12
-ROW_BYTES = 24
+ROW_BYTES = dict(dubins=24, reeds_shepp=24, polynomial=56, bezier=16)
+REF_CLASS = dict(dubins="Dubins", reeds_shepp="ReedsShepp", polynomial="Polynomial", bezier="Bezier")
 
 
-def poses(rng, n):
-    return np.column_stack([rng.uniform(0, 40, n), rng.uniform(0, 40, n), rng.uniform(-np.pi, np.pi, n)])
+def poses(rng, n, kind="dubins"):
+    cols = [rng.uniform(0, 40, n), rng.uniform(0, 40, n), rng.uniform(-np.pi, np.pi, n)]
+    if kind == "polynomial":
+        cols += [rng.uniform(0, 2, n), rng.uniform(-0.3, 0.3, n)]
+    return np.column_stack(cols)
+
+
+def kind_args(kind):
+    return POLY if kind == "polynomial" else BEZIER if kind == "bezier" else (STEP, CURV)
 
 
 def reference_seconds(src, s, g, kind="dubins"):
@@ -49,13 +63,13 @@ def reference_seconds(src, s, g, kind="dubins"):
     os.environ.setdefault("MPLBACKEND", "Agg")
     from python_motion_planning import curve_generation
 
-    gen = getattr(curve_generation, "ReedsShepp" if kind == "reeds_shepp" else "Dubins")(STEP, CURV)
+    gen = getattr(curve_generation, REF_CLASS[kind])(*kind_args(kind))
     secs, npts = [], []
     for a, b in zip(s, g):
         t0 = time.perf_counter()
         r = gen.generation(tuple(a), tuple(b))
         secs.append(time.perf_counter() - t0)
-        npts.append(len(r[2]))
+        npts.append(r.size if kind == "polynomial" else len(r[0]) if kind == "bezier" else len(r[2]))
     return dict(leg="reference_cpu_1core", kind=kind, pairs=len(secs), points=int(sum(npts)),
                 median_s_per_generation=float(np.median(secs)), min_s=float(min(secs)), max_s=float(max(secs)),
                 points_per_s=float(sum(npts) / sum(secs)))
@@ -63,7 +77,7 @@ def reference_seconds(src, s, g, kind="dubins"):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--kind", choices=("dubins", "reeds_shepp"), required=True)
+    ap.add_argument("--kind", choices=("dubins", "reeds_shepp", "polynomial", "bezier"), required=True)
     ap.add_argument("--matrix", type=int, default=1024)
     ap.add_argument("--segments", type=int, default=65536)
     ap.add_argument("--warmup", type=int, default=3)
@@ -83,29 +97,34 @@ def main():
         print(json.dumps(d), flush=True)
 
     rng = np.random.default_rng(0)
-    ms, mg = poses(rng, a.matrix), poses(rng, a.matrix)
-    ss, sg = poses(rng, a.segments), poses(rng, a.segments)
+    ms, mg = poses(rng, a.matrix, a.kind), poses(rng, a.matrix, a.kind)
+    ss, sg = poses(rng, a.segments, a.kind), poses(rng, a.segments, a.kind)
     if not torch.cuda.is_available():
         if not a.reference_src:
             raise SystemExit("needs a HIP device (there is no CPU fallback) or --reference-src")
     else:
-        from python_motion_planning_amd import Dubins, ReedsShepp, _lib, batch
+        from python_motion_planning_amd import Bezier, Dubins, Polynomial, ReedsShepp, _lib, batch
 
         L, ctx = _lib.load_library(), _lib.context()
         dev = [torch.as_tensor(v, device="cuda") for v in (ms, mg, ss, sg)]
-        rs = a.kind == "reeds_shepp"
-        entry = "pmp_reeds_shepp_batch" if rs else "pmp_dubins_batch"
-        run_batch = batch.reeds_shepp_batch if rs else batch.dubins_batch
-        run_matrix = batch.reeds_shepp_cost_matrix if rs else batch.dubins_cost_matrix
-        first = run_batch(dev[2], dev[3], STEP, CURV)
-        assert int((first["status"] != 0).sum()) == 0
+        args = kind_args(a.kind)
+        entry, run_batch, run_matrix, params, gen_cls, heads = dict(
+            dubins=("pmp_dubins_batch", batch.dubins_batch, batch.dubins_cost_matrix, _lib.DubinsParams, Dubins,
+                    ("word", "tpq", "cost")),
+            reeds_shepp=("pmp_reeds_shepp_batch", batch.reeds_shepp_batch, batch.reeds_shepp_cost_matrix,
+                         _lib.ReedsSheppParams, ReedsShepp, ("slot", "lengths", "cost", None)),
+            polynomial=("pmp_polycurve_batch", batch.polynomial_batch, batch.polynomial_time_matrix,
+                        lambda *p: _lib.PolyCurveParams(*p, 0.1, 1.0, 30.0), Polynomial, ("t_index", "T")),
+            bezier=("pmp_bezier_batch", batch.bezier_batch, None, _lib.BezierParams, Bezier, ("control",)))[a.kind]
+        first = run_batch(dev[2], dev[3], *args)
+        # a polynomial pair with no feasible T has status 1 and no rows: counted, not an error
+        assert int(((first["status"] != 0) & (first["status"] != 1)).sum()) == 0
         npts = int(first["n_points"].sum())
         pc = int(first["points"].shape[1])
-        prm = (_lib.ReedsSheppParams if rs else _lib.DubinsParams)(STEP, CURV)
-        o = {k: torch.empty_like(first[k]) for k in (("slot", "lengths") if rs else ("word", "tpq")) + ("cost", "n_points", "status")}
-        gen = (ReedsShepp if rs else Dubins)(STEP, CURV)
-        head = [o["slot"].data_ptr(), o["lengths"].data_ptr(), o["cost"].data_ptr(), None] if rs else \
-            [o["word"].data_ptr(), o["tpq"].data_ptr(), o["cost"].data_ptr()]
+        prm = params(*args)
+        o = {k: torch.empty_like(first[k]) for k in tuple(h for h in heads if h) + ("n_points", "status")}
+        gen = gen_cls(*args)
+        head = [None if h is None else o[h].data_ptr() for h in heads]
 
         def kernel():
             rc = getattr(L, entry)(ctx, _lib.stream_ptr(), ctypes.byref(prm), a.segments, dev[2].data_ptr(),
@@ -113,10 +132,12 @@ def main():
                                    o["status"].data_ptr())
             _lib.check(ctx, rc, entry)
 
-        legs = dict(cost_matrix=lambda: run_matrix(dev[0], dev[1], STEP, CURV), kernel=kernel,
-                    call=lambda: run_batch(dev[2], dev[3], STEP, CURV),
-                    cost_only=lambda: run_batch(dev[2], dev[3], STEP, CURV, cost_only=True),
+        legs = dict(cost_matrix=lambda: run_matrix(dev[0], dev[1], *args), kernel=kernel,
+                    call=lambda: run_batch(dev[2], dev[3], *args),
+                    cost_only=lambda: run_batch(dev[2], dev[3], *args, cost_only=True),
                     generation=lambda: gen.generation(tuple(ss[0]), tuple(sg[0])))
+        if run_matrix is None:
+            del legs["cost_matrix"]
         secs = {k: [] for k in legs}
         for rep in range(a.warmup + a.repeats):
             for k, fn in legs.items():
@@ -131,7 +152,7 @@ def main():
                 del r
                 if rep >= a.warmup:  # generation() ends in its own read-back: the host clock spans it
                     secs[k].append(host if k == "generation" else e0.elapsed_time(e1) * 1e-3)
-        assert int(o["n_points"].sum()) == npts and int((o["status"] != 0).sum()) == 0
+        assert int(o["n_points"].sum()) == npts and torch.equal(o["status"], first["status"])
         for k in legs:
             v = np.array(secs[k])
             med = float(np.median(v))
@@ -142,12 +163,15 @@ def main():
             elif k == "generation":
                 d.update(points=int(first["n_points"][0]), clock="host")
             else:
+                if a.kind == "polynomial":
+                    d.update(no_feasible_T=int((first["status"] == 1).sum()),
+                             median_t_index=float(first["t_index"].float().median()))
                 d.update(segments=a.segments, segments_per_s=a.segments / med)
                 if k != "cost_only":
                     d.update(points=npts, point_cap=pc, points_per_s=npts / med)
                 if k == "kernel":
-                    d.update(store_bytes=npts * ROW_BYTES, store_GBps=npts * ROW_BYTES / med * 1e-9,
-                             hbm_peak_frac=npts * ROW_BYTES / med / HBM_PEAK)
+                    rb = ROW_BYTES[a.kind]
+                    d.update(store_bytes=npts * rb, store_GBps=npts * rb / med * 1e-9, hbm_peak_frac=npts * rb / med / HBM_PEAK)
             emit(d)
     if a.reference_src:
         emit(reference_seconds(a.reference_src, ss[: a.reference_pairs], sg[: a.reference_pairs], a.kind))
