@@ -912,6 +912,81 @@ int pmp_bezier_batch(pmp_ctx* ctx, void* stream, const pmp_bezier_params* prm, i
                      const double* goal_xyyaw, double* control, int32_t* n_points, int point_cap, double* points,
                      int32_t* status);
 
+/* BSpline / BSpline3D(step, k, param_mode, spline_mode) (curve_generation/bspline_curve.py:26-37,
+ * bspline_curve3d.py:29-40) */
+enum { PMP_BSPLINE_CENTRIPETAL = 0, PMP_BSPLINE_CHORD_LENGTH = 1, PMP_BSPLINE_UNIFORM = 2 };
+enum { PMP_BSPLINE_INTERPOLATION = 0, PMP_BSPLINE_APPROXIMATION = 1 };
+enum { PMP_BSPLINE_2D = 0, PMP_BSPLINE_3D = 1 };
+typedef struct {
+    double step;
+    int32_t k;           /* degree, 1..5 */
+    int32_t param_mode;  /* PMP_BSPLINE_CENTRIPETAL .. */
+    int32_t spline_mode; /* PMP_BSPLINE_INTERPOLATION / _APPROXIMATION */
+    int32_t variant;     /* PMP_BSPLINE_2D: BSpline's rules, PMP_BSPLINE_3D: BSpline3D's */
+} pmp_bspline_params;
+
+/*
+ * Batched B-spline curves through (or near) waypoint lists.  Replaces BSpline(...).run(points) and
+ * BSpline3D(...).run(points) for n_curves lists in one launch, one wave per curve: paramSelection,
+ * knotGeneration, interpolation or approximation (then parameters and knots again from the control polygon, as
+ * run() does), generation at np.linspace(0, 1, n_samples) with the last row's N[-1][-1] = 1, and the rows'
+ * polyline length (hypot of x and y; the 3D variant on 3D points: the Euclidean norm).
+ * The two variants differ in: the segment length (2D: math.hypot of x and y; 3D: the Euclidean norm over dim
+ * coordinates), the guard `s[-1] > 0` (3D only: coinciding points give parameters 0 and a singular system; 2D
+ * divides 0 / 0 and every control point and row is NaN, status 0), n_samples (2D: int(1 / step), 3D: at least 2)
+ * and the length.  The basis values are the reference's bits (its expressions in its order over the k + 1
+ * functions that can be non-zero); the linear systems are solved by banded elimination without pivoting,
+ * the reference inverts with LAPACK: control points and rows agree to rounding times the system's condition.
+ *   pts [sum n][dim] f64 packed waypoints, off [n_curves + 1] i32 their offsets; dim 2 or 3
+ *   min_waypoints / max_waypoints: the shortest and longest curve of the launch, by the caller's own
+ *       count (the offsets are on the device); max_waypoints sizes the LDS and the outputs' rows.  A curve found
+ *       outside them is not run: status 4, n_control 0
+ *   params_in [n_curves][max_waypoints], knot_in [n_curves][max_waypoints + k + 1] nullable: use these
+ *       parameters / knots for the solve instead of computing them (interpolation(points, param, knot))
+ *   params [n_curves][max_waypoints], knot [n_curves][max_waypoints + k + 1], control [n_curves][max_waypoints][dim],
+ *   n_control [n_curves]: what generation() was given (approximation: n - 1 control points and the second
+ *       parameters and knots); entries past a curve's own count are 0
+ *   n_samples: int(1 / step) (3D: max(2, .)), computed by the caller too, since it sizes points
+ *   points [n_curves][n_samples][dim] nullable: NULL = control points, length and status only
+ *   length [n_curves], status [n_curves]: 0 ok, 4 the reference raises numpy.linalg.LinAlgError (a pivot that
+ *       is exactly zero: a repeated consecutive waypoint, n <= k, coinciding points in 3D); control, rows
+ *       and length are then NaN
+ * Refused with PMP_EINVAL: k outside 1..5; step <= 0 or non-finite; more than 2^24 samples; no sample (2D,
+ * step > 1: the reference raises IndexError); n_samples not int(1 / step); dim not 2 or 3; fewer than 2 or more
+ * than 64 waypoints; approximation with fewer than k + 2 (the reference's precondition N > H > k); unknown
+ * modes; null pointers; n_curves < 0.
+ */
+int pmp_bspline_batch(pmp_ctx* ctx, void* stream, const pmp_bspline_params* prm, int n_curves, const double* pts,
+                      const int32_t* off, int dim, int min_waypoints, int max_waypoints, const double* params_in,
+                      const double* knot_in, double* params, double* knot, double* control, int32_t* n_control,
+                      int n_samples, double* points, double* length, int32_t* status);
+
+/* CubicSpline(step) (curve_generation/cubic_spline.py:26-27) */
+typedef struct {
+    double step;
+    int32_t with_derivative; /* rows of 5 (x, y, yaw, dx, dy) instead of 3 */
+    int32_t pad_;
+} pmp_cubic_spline_params;
+
+/*
+ * Batched natural cubic splines over arc length.  Replaces CubicSpline(step).run(points) (:84-111) for n_lists
+ * waypoint lists, one wave per list: s = [0] + cumsum(hypot) bit for bit (CPython's hypot, left to right),
+ * n_points = len(np.arange(0, s[-1], step)) = ceil(s[-1] / step), the spline coefficients of x(s) and y(s)
+ * (:46-67; the tridiagonal system by the Thomas algorithm, the reference by a dense LAPACK solve: rounding
+ * apart), and one row per t_i = i step: the interval bisect(s, t) - 1, x, y, yaw = atan2(dy, dx).
+ *   pts [sum n][dim] f64 packed waypoints (x, y first), off [n_lists + 1] i32; dim 2 or 3
+ *   arc_length [n_lists]  s[-1]
+ *   n_points [n_lists], points [n_lists][point_cap][3 or 5] nullable (NULL = counts and arc length only)
+ *   status [n_lists]  0 ok (a repeated consecutive waypoint divides by zero: the full count of NaN rows, as the
+ *       reference), 2 point_cap too small (the count is reported, the first point_cap rows are valid), 4 the
+ *       reference raises (np.arange of a non-finite s[-1]) or the list has more than 2^24 points
+ * Refused with PMP_EINVAL: step <= 0 or non-finite; dim not 2 or 3; fewer than 2 or more than 512 waypoints;
+ * null pointers; n_lists < 0; point_cap < 1.
+ */
+int pmp_cubic_spline_batch(pmp_ctx* ctx, void* stream, const pmp_cubic_spline_params* prm, int n_lists, const double* pts,
+                           const int32_t* off, int dim, int min_waypoints, int max_waypoints, double* arc_length,
+                           int32_t* n_points, int point_cap, double* points, int32_t* status);
+
 /* Launch-span recording for profiling: while set, every A* 2D launch of this context folds its
  * workers' first start and last end wall-clock ticks into span[0] (atomic min) and span[1] (atomic
  * max); the caller initialises span to {UINT64_MAX, 0}.  NULL switches it off. */

@@ -92,6 +92,9 @@ SIGNATURES = {
     "pmp_polycurve_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "pmp_polycurve_time_matrix": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "pmp_bezier_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "pmp_bspline_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp,
+                               _vp]),
+    "pmp_cubic_spline_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
 }
 
 
@@ -233,6 +236,23 @@ class PolyCurveParams(ctypes.Structure):
 class BezierParams(ctypes.Structure):
     """pmp_bezier_params == Bezier(step, offset) (curve_generation/bezier_curve.py:27-29)."""
     _fields_ = [("step", ctypes.c_double), ("offset", ctypes.c_double)]
+
+
+BSPLINE_PARAM_MODES = ("centripetal", "chord_length", "uniform_spaced")
+BSPLINE_SPLINE_MODES = ("interpolation", "approximation")
+
+
+class BSplineParams(ctypes.Structure):
+    """pmp_bspline_params == BSpline / BSpline3D(step, k, param_mode, spline_mode) (curve_generation/
+    bspline_curve.py:26-37); the modes as indices into BSPLINE_PARAM_MODES / BSPLINE_SPLINE_MODES, variant 0 the
+    2D class's rules, 1 BSpline3D's."""
+    _fields_ = [("step", ctypes.c_double), ("k", ctypes.c_int32), ("param_mode", ctypes.c_int32),
+                ("spline_mode", ctypes.c_int32), ("variant", ctypes.c_int32)]
+
+
+class CubicSplineParams(ctypes.Structure):
+    """pmp_cubic_spline_params == CubicSpline(step) (curve_generation/cubic_spline.py:26-27)."""
+    _fields_ = [("step", ctypes.c_double), ("with_derivative", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
 TRACK_LQR, TRACK_MPC = 0, 1

@@ -1316,3 +1316,126 @@ def bezier_batch(starts, goals, step: float, offset: float, cost_only: bool = Fa
     if retry_overflow and n and not cost_only:
         _retry_overflowed(torch, out, n, point_cap, 2, lambda redo, idx, pc: launch(s[idx].contiguous(), g[idx].contiguous(), pc))
     return out
+
+
+def _pack_waypoints(torch, curves, entry, dims=(2, 3)):
+    """The waypoint lists of a launch as (flat [sum n, dim] f64, off [m + 1] i32 device tensors, host off, dim):
+    `curves` is a list of [n, dim] arrays (one dim for all) or (flat, off) already packed that way."""
+    if isinstance(curves, tuple) and len(curves) == 2 and hasattr(curves[1], "dtype") and getattr(curves[1], "ndim", 0) == 1:
+        flat = _dev(torch, curves[0], torch.float64)
+        flat = flat.reshape(-1, flat.shape[-1]) if flat.dim() >= 2 else flat.reshape(0, 2)
+        off = _dev(torch, curves[1], torch.int32).reshape(-1)
+        host = off.cpu().numpy()
+    else:
+        arrs = [np.asarray(c, np.float64) for c in curves]
+        arrs = [a.reshape(-1, a.shape[-1] if a.ndim >= 2 else 2) for a in arrs]
+        if len({a.shape[1] for a in arrs}) > 1:
+            raise ValueError(f"{entry}: every curve of a launch must have the same dimension")
+        host = np.zeros(len(arrs) + 1, np.int32)
+        host[1:] = np.cumsum([len(a) for a in arrs])
+        flat = torch.as_tensor(np.concatenate(arrs) if arrs else np.zeros((0, 2)), device="cuda")
+        off = torch.as_tensor(host, device="cuda")
+    if len(host) < 1 or host[0] != 0 or np.any(np.diff(host) < 0) or int(host[-1]) != int(flat.shape[0]):
+        raise ValueError(f"{entry}: off must rise from 0 to the number of packed waypoints")
+    return flat, off, host, int(flat.shape[1])
+
+
+def bspline_samples(step: float, three_d: bool = False) -> int:
+    """len(t) of BSpline.run (bspline_curve.py:232: int(1 / step)) or BSpline3D.run (at least 2)."""
+    n = int(1 / step)
+    return max(2, n) if three_d else n
+
+
+def bspline_batch(curves, step: float, k: int, param_mode: str = "centripetal", spline_mode: str = "interpolation",
+                  cost_only: bool = False, three_d: bool = False, params=None, knot=None):
+    """Batched BSpline(step, k, param_mode, spline_mode).run(points) (curve_generation/bspline_curve.py:219-271),
+    or BSpline3D's with three_d (bspline_curve3d.py:164-220), on pmp_bspline_batch: one wave per curve.
+    curves: list of [n, 2 | 3] waypoint arrays, or (flat [sum n, dim], off [m + 1] i32) device tensors.
+    params [m, n_max] / knot [m, n_max + k + 1] (optional): use these instead of paramSelection / knotGeneration.
+    Returns dict of device tensors: params [m, n_max], knot [m, n_max + k + 1], control [m, n_max, dim],
+    n_control [m], points [m, T, dim] (None with cost_only), length [m], status [m] (include/pmp.h: 4 where the
+    reference raises LinAlgError), and n_samples = T, the same for every curve."""
+    torch, L, ctx = _open()
+    entry = "pmp_bspline_batch"
+    if param_mode not in _lib.BSPLINE_PARAM_MODES or spline_mode not in _lib.BSPLINE_SPLINE_MODES:
+        raise ValueError("unknown param_mode / spline_mode")
+    flat, off, host, dim = _pack_waypoints(torch, curves, entry)
+    m = len(host) - 1
+    counts = np.diff(host)
+    lo, hi = (int(counts.min()), int(counts.max())) if m else (2, 2)
+    step = float(step)
+    T = bspline_samples(step, three_d) if step > 0 and math.isfinite(step) and 1 / step <= 1 << 24 else 0
+    prm = _lib.BSplineParams(step, int(k), _lib.BSPLINE_PARAM_MODES.index(param_mode),
+                             _lib.BSPLINE_SPLINE_MODES.index(spline_mode), 1 if three_d else 0)
+    nm = max(hi, 2)
+    nk = nm + max(int(k), 0) + 1
+    f64 = dict(dtype=torch.float64, device="cuda")
+    i32 = dict(dtype=torch.int32, device="cuda")
+    pin = None if params is None else _dev(torch, params, torch.float64).reshape(m, nm)
+    kin = None if knot is None else _dev(torch, knot, torch.float64).reshape(m, nk)
+    out = dict(params=torch.empty((m, nm), **f64), knot=torch.empty((m, nk), **f64),
+               control=torch.empty((m, nm, dim), **f64), n_control=torch.empty(m, **i32),
+               points=None if cost_only else torch.empty((m, max(T, 0), dim), **f64), length=torch.empty(m, **f64),
+               status=torch.empty(m, **i32), n_samples=T)
+    rc = L.pmp_bspline_batch(ctx, _lib.stream_ptr(), ctypes.byref(prm), m, flat.data_ptr(), off.data_ptr(), dim, lo, hi,
+                             _lib.ptr(pin), _lib.ptr(kin), out["params"].data_ptr(), out["knot"].data_ptr(),
+                             out["control"].data_ptr(), out["n_control"].data_ptr(), T, _lib.ptr(out["points"]),
+                             out["length"].data_ptr(), out["status"].data_ptr())
+    _lib.check(ctx, rc, entry)
+    return out
+
+
+def cubic_spline_batch(curves, step: float, cost_only: bool = False, point_cap: int | None = None,
+                       retry_overflow: bool = True, with_derivative: bool = False):
+    """Batched CubicSpline(step).run(points) (curve_generation/cubic_spline.py:84-111) on
+    pmp_cubic_spline_batch: one wave per waypoint list.  curves: list of [n, 2 | 3] arrays (x, y first), or
+    (flat, off) device tensors.  Returns dict of device tensors: arc_length [m] (s[-1]), n_points [m], points
+    [m, point_cap, 3] (x, y, yaw; 5 columns with with_derivative: dx, dy too; None with cost_only), status
+    (include/pmp.h: 4 where np.arange raises).  Lists whose points overflow the first cap are re-run with
+    their exact count when retry_overflow."""
+    torch, L, ctx = _open()
+    entry = "pmp_cubic_spline_batch"
+    flat, off, host, dim = _pack_waypoints(torch, curves, entry)
+    m = len(host) - 1
+    step = float(step)
+    prm = _lib.CubicSplineParams(step, 1 if with_derivative else 0, 0)
+    row = 5 if with_derivative else 3
+    if point_cap is None:  # the polyline's length / step, from the device's own rounding of it, plus slack
+        point_cap = 1
+        if m and int(flat.shape[0]) >= 2 and step > 0 and math.isfinite(step):
+            d = flat[1:, :2] - flat[:-1, :2]
+            seg = torch.hypot(d[:, 0], d[:, 1])
+            seg[torch.as_tensor(host[1:-1].astype(np.int64) - 1, device="cuda")] = 0  # the joints between lists
+            cs = torch.cat([torch.zeros(1, **dict(dtype=torch.float64, device="cuda")), torch.cumsum(seg, 0)])
+            o = torch.as_tensor(host.astype(np.int64), device="cuda")
+            tot = cs[torch.clamp(o[1:] - 1, min=0)] - cs[torch.clamp(o[:-1], max=int(flat.shape[0]) - 1)]
+            est = torch.ceil(tot / step) + 1
+            est = torch.where(torch.isfinite(est) & (est < float(1 << 24)), est, torch.ones_like(est))
+            point_cap = max(int(est.max().item()), 1)
+    point_cap = max(int(point_cap), 1)
+
+    def launch(flat, off, host, pc):
+        n = len(host) - 1
+        counts = np.diff(host)
+        lo, hi = (int(counts.min()), int(counts.max())) if n else (2, 2)
+        f64 = dict(dtype=torch.float64, device="cuda")
+        i32 = dict(dtype=torch.int32, device="cuda")
+        o = dict(arc_length=torch.empty(n, **f64), n_points=torch.empty(n, **i32),
+                 points=None if cost_only else torch.empty((n, pc, row), **f64), status=torch.empty(n, **i32))
+        rc = L.pmp_cubic_spline_batch(ctx, _lib.stream_ptr(), ctypes.byref(prm), n, flat.data_ptr(), off.data_ptr(), dim,
+                                      lo, hi, o["arc_length"].data_ptr(), o["n_points"].data_ptr(), pc,
+                                      _lib.ptr(o["points"]), o["status"].data_ptr())
+        _lib.check(ctx, rc, entry)
+        return o
+
+    def rerun(redo, idx, pc):
+        cnt = np.diff(host)[redo]
+        rows = torch.as_tensor(np.concatenate([np.arange(host[i], host[i + 1], dtype=np.int64) for i in redo]), device="cuda")
+        h2 = np.zeros(len(redo) + 1, np.int32)
+        h2[1:] = np.cumsum(cnt)
+        return launch(flat[rows].contiguous(), torch.as_tensor(h2, device="cuda"), h2, pc)
+
+    out = launch(flat, off, host, point_cap)
+    if retry_overflow and m and not cost_only:
+        _retry_overflowed(torch, out, m, point_cap, row, rerun)
+    return out

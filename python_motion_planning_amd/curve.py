@@ -5,6 +5,12 @@
   ReedsShepp curve_generation/reeds_shepp.py:13-736 pmp_reeds_shepp_batch / pmp_reeds_shepp_cost_matrix
   Polynomial curve_generation/polynomial_curve.py:13-195 pmp_polycurve_batch / pmp_polycurve_time_matrix
   Bezier   curve_generation/bezier_curve.py:13-111 pmp_bezier_batch
+  BSpline  curve_generation/bspline_curve.py:12-271 pmp_bspline_batch
+  BSpline3D curve_generation/bspline_curve3d.py:13-220 pmp_bspline_batch (its own rules)
+  CubicSpline curve_generation/cubic_spline.py:13-128 pmp_cubic_spline_batch
+
+The first four take pose pairs, the last three a whole waypoint list: run(points) without yaw, run_batch for
+many lists in one launch (batch.bspline_batch / batch.cubic_spline_batch).
 
 Same constructor, generation() return values and run() input (yaw in degrees) as the reference; run() does
 not plot (as Planner.run, planner.py:31-33).  Many pose pairs at once: generation_batch and cost_matrix of
@@ -12,7 +18,7 @@ either class, or batch.dubins_batch / batch.dubins_cost_matrix and batch.reeds_s
 batch.reeds_shepp_cost_matrix.  Dubins.generation() returns its cost in curvature-normalised units and
 ReedsShepp.generation() in the units of x and y, as the reference's do.  Polynomial takes 5-tuples (x, y,
 yaw, v, a) and has generation_batch and time_matrix; Bezier has generation_batch.  CurveFactory builds
-"dubins" only: construct ReedsShepp, Polynomial and Bezier directly.  There is no CPU fallback: without the library or a HIP device the calls
+"dubins" only: construct ReedsShepp, Polynomial, Bezier, BSpline, BSpline3D and CubicSpline directly.  There is no CPU fallback: without the library or a HIP device the calls
 raise PMPError.
 """
 from __future__ import annotations
@@ -360,3 +366,196 @@ class Bezier(Curve):
                 path_x.append(pt[0])
                 path_y.append(pt[1])
         return path_x, path_y
+
+
+class BSpline(Curve):
+    """B-spline curve generation through a waypoint list (bspline_curve.py:12-271).
+
+    Parameters:
+        step (float): Simulation or interpolation size: int(1 / step) samples
+        k (int): Degree of curve (1..5 on the kernel)
+        param_mode (str): "centripetal" | "chord_length" | "uniform_spaced"
+        spline_mode (str): "interpolation" | "approximation"
+
+    run() and the four stage methods read their result from one launch of pmp_bspline_batch (at most 64
+    waypoints; the entry refuses more with PMPError); generation() and baseFunction() run on the host.
+    approximation with fewer than k + 2 waypoints, outside the reference's own precondition N > H > k, raises
+    NotImplementedError.
+    """
+
+    _three_d = False
+
+    def __init__(self, step: float, k: int, param_mode: str = "centripetal", spline_mode: str = "interpolation") -> None:
+        super().__init__(step)
+        self.k = k
+        assert param_mode in _lib.BSPLINE_PARAM_MODES, "Parameter selection mode error!"
+        self.param_mode = param_mode
+        assert spline_mode in _lib.BSPLINE_SPLINE_MODES, "Spline mode selection error!"
+        self.spline_mode = spline_mode
+
+    def __str__(self) -> str:
+        return "B-Spline Curve"
+
+    def baseFunction(self, i: int, k: int, t: float, knot: list):
+        """N_{i,k}(t) by the Cox-de Boor recursion with the reference's half-open degree-0 test and its
+        zero-length guards (:42-70), on the host."""
+        if k == 0:
+            return 1.0 if knot[i] <= t < knot[i + 1] else 0.0
+        left, right = knot[i + k] - knot[i], knot[i + k + 1] - knot[i + 1]
+        value = 0.0
+        if left:
+            value = (t - knot[i]) / left * self.baseFunction(i, k - 1, t, knot)
+        if right:
+            value = value + (knot[i + k + 1] - t) / right * self.baseFunction(i + 1, k - 1, t, knot)
+        return value
+
+    def _cut(self, points):
+        """The waypoints as an [n, 2] array: the 2D class keeps x and y (:229-230)."""
+        return np.asarray([(p[0], p[1]) for p in points], np.float64).reshape(-1, 2)
+
+    def _stage(self, points, spline_mode="interpolation", params=None, knot=None):
+        """One launch without samples for the stage methods: its outputs on the host."""
+        r = batch.bspline_batch([self._cut(points)], 0.5, self.k, self.param_mode, spline_mode, cost_only=True,
+                                three_d=self._three_d, params=params, knot=knot)
+        return {key: v.cpu().numpy()[0] for key, v in r.items() if hasattr(v, "cpu")}
+
+    def paramSelection(self, points: list):
+        """The parameters of the waypoints as a list (:72-104)"""
+        return self._stage(points)["params"][: len(points)].tolist()
+
+    def knotGeneration(self, param: list, n: int):
+        """The knot vector [n + k + 1] of n parameters as a list (:106-127)"""
+        r = self._stage(np.zeros((n, 2)), params=np.asarray(param, np.float64)[None, :n])
+        return r["knot"][: n + self.k + 1].tolist()
+
+    def _given(self, points, param, knot):
+        n = len(points)
+        return (np.asarray(param, np.float64)[None, :n], np.asarray(knot, np.float64)[None, : n + self.k + 1])
+
+    def interpolation(self, points: list, param: list, knot: list):
+        """The n control points of the curve through the waypoints, as an array [n, dim] (:129-154)"""
+        p, kn = self._given(points, param, knot)
+        r = self._stage(points, params=p, knot=kn)
+        if r["status"] == _lib.STATUS_REF_RAISES:
+            raise np.linalg.LinAlgError("Singular matrix")
+        return r["control"][: len(points)].copy()
+
+    def approximation(self, points: list, param: list, knot: list):
+        """The n - 1 control points of the least-squares curve with fixed ends, as an array (:156-195)"""
+        if len(points) < self.k + 2:
+            raise NotImplementedError("approximation needs at least k + 2 waypoints (N > H > k)")
+        p, kn = self._given(points, param, knot)
+        r = self._stage(points, "approximation", params=p, knot=kn)
+        if r["status"] == _lib.STATUS_REF_RAISES:
+            raise np.linalg.LinAlgError("Singular matrix")
+        return r["control"][: len(points) - 1].copy()
+
+    def generation(self, t, k, knot, control_pts):
+        """The curve's points at the parameter values t, as an array [len(t), dim] (:197-217), on the host."""
+        control_pts = np.asarray(control_pts)
+        N = np.array([[self.baseFunction(j, k, ti, knot) for j in range(len(control_pts))] for ti in t], np.float64)
+        N = N.reshape(len(t), len(control_pts))
+        N[len(t) - 1][len(control_pts) - 1] = 1
+        return N @ control_pts
+
+    def run_batch(self, point_lists, **kw):
+        """run() of many waypoint lists (all 2D or all 3D) in one launch: a list of run()'s results."""
+        lists = [self._cut(p) for p in point_lists]
+        for p in lists:
+            assert len(p) >= 2, "Number of points should be at least 2."
+        if batch.bspline_samples(self.step, self._three_d) == 0:  # N[len(t) - 1] of an empty N (:215)
+            raise IndexError("index -1 is out of bounds for axis 0 with size 0")
+        if self.spline_mode == "approximation" and any(len(p) < self.k + 2 for p in lists):
+            raise NotImplementedError("approximation needs at least k + 2 waypoints (N > H > k)")
+        r = batch.bspline_batch(lists, self.step, self.k, self.param_mode, self.spline_mode, three_d=self._three_d, **kw)
+        if np.any(r["status"].cpu().numpy() == _lib.STATUS_REF_RAISES):  # np.linalg.inv (:150, :191)
+            raise np.linalg.LinAlgError("Singular matrix")
+        return [[tuple(row) for row in curve] for curve in r["points"].cpu().numpy().tolist()]
+
+    def run(self, points: list, display: bool = True):
+        """The curve through (or near) `points` (:219-271): [(x, y), ...] of Python floats; 3-tuples are cut
+        to (x, y).  Nothing is plotted, whatever `display` says."""
+        assert len(points) >= 2, "Number of points should be at least 2."
+        return self.run_batch([points])[0]
+
+
+class BSpline3D(BSpline):
+    """B-spline curve generation in 2D or 3D (bspline_curve3d.py:13-220): BSpline with the Euclidean norm in
+    the points' own dimension, parameters 0 where all points coincide, and at least two samples.  run() returns
+    tuples in the native dimension."""
+
+    _three_d = True
+
+    def __str__(self) -> str:
+        return "B-Spline Curve 3D"
+
+    def _cut(self, points):
+        P = np.asarray(points, dtype=np.float64)
+        P = P.reshape(len(P), -1)
+        assert P.shape[1] in (2, 3), "BSpline3D supports 2D or 3D points."
+        return P
+
+
+class CubicSpline(Curve):
+    """Cubic spline generation through a waypoint list, parametrised by arc length (cubic_spline.py:13-128).
+
+    Parameters:
+        step (float): Simulation or interpolation size
+    """
+
+    def __init__(self, step: float) -> None:
+        super().__init__(step)
+
+    def __str__(self) -> str:
+        return "Cubic Spline"
+
+    def spline(self, x_list: list, y_list: list, t: list):
+        """The natural cubic spline y(x) through (x_list, y_list) at the values of t inside
+        [x_list[0], x_list[-1]]: (p, dp), its values and first derivatives (:32-79), on the host."""
+        x, a = np.asarray(x_list, np.float64), np.asarray(y_list, np.float64)
+        h, num = np.diff(x), len(x)
+        A, B = np.zeros((num, num)), np.zeros(num)
+        A[0, 0] = A[num - 1, num - 1] = 1.0
+        for i in range(1, num - 1):
+            A[i, i - 1 : i + 2] = h[i - 1], 2.0 * (h[i - 1] + h[i]), h[i]
+            B[i] = 3.0 * (a[i + 1] - a[i]) / h[i] - 3.0 * (a[i] - a[i - 1]) / h[i - 1]
+        c = np.linalg.solve(A, B)
+        d = [(c[i + 1] - c[i]) / (3.0 * h[i]) for i in range(num - 1)]
+        b = [(a[i + 1] - a[i]) / h[i] - h[i] * (c[i + 1] + 2.0 * c[i]) / 3.0 for i in range(num - 1)]
+        p, dp = [], []
+        for it in t:
+            if it < x[0] or it > x[-1]:
+                continue
+            i = int(np.searchsorted(x, it, side="right")) - 1
+            dx = it - x[i]
+            p.append(a[i] + b[i] * dx + c[i] * dx ** 2 + d[i] * dx ** 3)
+            dp.append(b[i] + 2.0 * c[i] * dx + 3.0 * d[i] * dx ** 2)
+        return p, dp
+
+    def generation(self, start_pose: tuple, goal_pose: tuple):
+        pass
+
+    def _xy(self, points):
+        if len(points[0]) not in (2, 3):
+            raise NotImplementedError
+        return np.asarray([(p[0], p[1]) for p in points], np.float64).reshape(-1, 2)
+
+    def run_batch(self, point_lists, **kw):
+        """run() of many waypoint lists in one launch: a list of (path_x, path_y, path_yaw)."""
+        lists = []
+        for p in point_lists:
+            assert len(p) >= 2, "Number of points should be at least 2."
+            lists.append(self._xy(p))
+        r = batch.cubic_spline_batch(lists, self.step, **kw)
+        if np.any(r["status"].cpu().numpy() == _lib.STATUS_REF_RAISES):  # np.arange(0, s[-1], step) (:107)
+            raise ValueError("arange: cannot compute length")
+        npt, pts = r["n_points"].cpu().numpy(), r["points"].cpu().numpy()
+        return [(pts[i, : npt[i], 0].tolist(), pts[i, : npt[i], 1].tolist(), pts[i, : npt[i], 2].tolist())
+                for i in range(len(lists))]
+
+    def run(self, points: list):
+        """The spline through `points` [(x, y) or (x, y, anything)] (:84-111), sampled every `step` of arc
+        length.  Returns (path_x, path_y, path_yaw) as lists: the reference only plots them and returns None;
+        returning the path follows Dubins.run here.  Nothing is plotted."""
+        assert len(points) >= 2, "Number of points should be at least 2."
+        return self.run_batch([points])[0]
