@@ -617,7 +617,7 @@ typedef struct {
  * t = 0, dt, ... (+ total_time) through interp1d (:304-335), yaw / yaw rate
  * (trajectory_base.py:245-261).  Values match the reference to rounding.
  *   path_xyz [sum n][3] f64, path_off [nq + 1] i32   waypoints per path (reference order)
- *   max_waypoints  >= every path's n (sizes LDS; <= 480)
+ *   max_waypoints  >= every path's n (sizes LDS; <= 602)
  *   s_values, s_dot, s_ddot, time_profile [nq][sample_cap]; n_samples [nq] = max(int(L / res), 100)
  *   points [nq][point_cap][12]: time, position[3], velocity[3], acceleration[3], yaw, yaw rate
  *       (NaN where the reference leaves None); n_points [nq]; total_time [nq]

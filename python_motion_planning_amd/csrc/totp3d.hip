@@ -14,6 +14,7 @@
 //     rate from the neighbouring lane.
 // Values follow the reference's operation order (CPython / numpy float64, -ffp-contract=off), so
 // results match it to rounding (the parity tests bound them at 1e-9 relative).
+#include <string>
 #include "pmp_internal.h"
 #include "traj_sample.h"
 
@@ -180,6 +181,17 @@ __device__ __forceinline__ double lin(double L, int ns, int i)
 }
 
 __device__ __forceinline__ double sq(double a) { return a * a; }
+
+// LDS of a launch: arc + coefficients + the path / spline-solve region (the 64-sample stage fits inside it)
+constexpr size_t lds_bytes(int max_waypoints)
+{
+    const size_t nm = (size_t)max_waypoints;
+    const size_t work = 3 * nm + 3 * nm + 15 * nm;
+    return 8 * (nm + 12 * (nm > 1 ? nm - 1 : 1) + (work > (size_t)kCh * kStage + 8 ? work : (size_t)kCh * kStage + 8));
+}
+constexpr size_t kLdsBytes = 160 * 1024;  // one CU's LDS
+constexpr int kMaxWp = 602;               // the most waypoints whose block fits it: 8 (34 n - 12) bytes
+static_assert(lds_bytes(kMaxWp) <= kLdsBytes && lds_bytes(kMaxWp + 1) > kLdsBytes, "kMaxWp is the LDS bound");
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void totp3d_kernel(pmp_totp_params T, int nq, const double* __restrict__ path,
                                                     const int32_t* __restrict__ off, int nmax, int sample_cap,
@@ -492,12 +504,10 @@ extern "C" int pmp_totp3d_batch(pmp_ctx* ctx, void* stream, const pmp_totp_param
     if (!path_xyz || !path_off || !s_values || !s_dot || !s_ddot || !time_profile || !n_samples || !points ||
         !n_points || !total_time || !status)
         return pmp_set_err(ctx, PMP_EINVAL, "pmp_totp3d_batch: null pointer argument");
-    // LDS: arc + coefficients + the path / spline-solve region (the 64-sample stage fits inside it)
-    const size_t nm = (size_t)max_waypoints;
-    const size_t work = 3 * nm + 3 * nm + 15 * nm;
-    const size_t lds = 8 * (nm + 12 * (nm > 1 ? nm - 1 : 1) + (work > (size_t)kCh * kStage + 8 ? work : (size_t)kCh * kStage + 8));
-    if (lds > 160 * 1024)
-        return pmp_set_err(ctx, PMP_EINVAL, "pmp_totp3d_batch: max_waypoints too large for one CU's LDS (<= 480)");
+    const size_t lds = lds_bytes(max_waypoints);
+    if (lds > kLdsBytes)
+        return pmp_set_err(ctx, PMP_EINVAL, "pmp_totp3d_batch: max_waypoints too large for one CU's LDS (<= " +
+                                                std::to_string(kMaxWp) + ")");
     PMP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipLaunchKernelGGL(totp3d_kernel, dim3(nq), dim3(64), lds, (hipStream_t)stream, *prm, nq, path_xyz, path_off,
                        max_waypoints, sample_cap, s_values, s_dot, s_ddot, time_profile, n_samples, point_cap, points,
