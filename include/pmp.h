@@ -987,6 +987,62 @@ int pmp_cubic_spline_batch(pmp_ctx* ctx, void* stream, const pmp_cubic_spline_pa
                            const int32_t* off, int dim, int min_waypoints, int max_waypoints, double* arc_length,
                            int32_t* n_points, int point_cap, double* points, int32_t* status);
 
+/* PSO(start, goal, env, n_particles, point_num, w_inertial, w_cognitive, w_social, max_speed, max_iter)
+ * (global_planner/evolutionary_search/pso.py:44-61) and the grid's ranges */
+typedef struct {
+    int32_t x_range, y_range;
+    int32_t n_particles;
+    int32_t point_num; /* 1..62: with start and goal at most 64 waypoints */
+    int32_t max_iter;
+    int32_t waves;     /* wave64s per workgroup, 1..16; 0 = pmp_pso_default_waves(), or fewer: no more than there are
+                          particles or than the LDS holds beside the swarm.  Results do not depend on it */
+    double w_inertial, w_cognitive, w_social;
+    double max_speed;
+} pmp_pso_params;
+
+/*
+ * Batched particle-swarm plans on one grid.  Replaces PSO.plan() (pso.py:77-123) after initializePositions()
+ * for n_plans independent plans in one launch, one workgroup per plan: the initial fitness of every particle,
+ * max_iter iterations of optimizeParticle over the particles in index order (a particle that beats the global
+ * best replaces it at once, for the particles after it too), and the best particle's curve.  The curve is
+ * BSpline(step=0.01, k=4)'s (centripetal interpolation, 100 rows) through [start] + position + [goal] with
+ * repeated points dropped; the fitness is 100000 / (length + 50000 obs_cost), obs_cost the number of the 99
+ * consecutive pairs of round()ed rows for which PSO.isCollision holds, and inf where the curve raises (fewer
+ * than 5 points left, or a singular collocation matrix).  best_pos is position in the reference (the same
+ * list), so the cognitive term is w_cognitive * rand1 * 0.  Positions, velocities and every decision are the
+ * reference's exactly as long as no two compared fitness values lie within the curve's rounding of each other
+ * and no row coordinate within it of a half-integer; fitness values, rows and length agree to that rounding.
+ * An iteration evaluates the particles not yet committed in parallel against the global best as it stands and
+ * repeats those after the first one that replaces it; the result is the sequential one for any `waves`.
+ *   occ_bits: the grid's bit-packed x-major occupancy (cell x * y_range + y), as for pmp_astar2d_batch
+ *   start, goal [n_plans][2] i32; init_positions [n_plans][n_particles][point_num][2] i32 (initializePositions())
+ *   init_bounds: HOST int32[4] = min x, min y, max x, max y over init_positions, by the caller's own count (the
+ *       positions are on the device).  A plan found with a position outside the grid is not run: status 4,
+ *       best_fitness and length NaN, nothing else written
+ *   rnd [n_plans][rnd_stride] f64: each plan's random.random() stream; particle p's point i at iteration t
+ *       reads rand1, rand2 at 2 ((t n_particles + p) point_num + i); 2 point_num n_particles max_iter draws
+ *   status [n_plans]: 0, or 4 where the best fitness is inf (plan() raises the curve's LinAlgError at its last line)
+ *   best_position [n_plans][point_num][2] i32, best_fitness [n_plans], fitness_history [n_plans][max_iter]
+ *   positions [n_plans][n_particles][point_num][2] i32, velocities (same shape) f64, fitness and
+ *   particle_best_fitness [n_plans][n_particles]: the final swarm
+ *   points [n_plans][100][2], length [n_plans]: the best particle's curve (NaN with status 4)
+ *   repeats [n_plans] i64: evaluations thrown away because an earlier particle replaced the global best
+ *   trace_positions [n_plans][max_iter][n_particles][point_num][2] i32 and trace_fitness
+ *       [n_plans][max_iter][n_particles], both nullable (together): the swarm after every iteration
+ * Refused with PMP_EINVAL: x_range or y_range < 1; n_particles < 1; point_num outside 1..62; max_iter < 0; a
+ * non-finite weight; max_speed < 0 or NaN; waves outside 0..16; init_bounds outside the grid; rnd_stride below
+ * the draw count; a swarm whose LDS (two copies of its state beside `waves` B-spline states) exceeds 160 KiB;
+ * null pointers; n_plans < 0.
+ */
+int pmp_pso_batch(pmp_ctx* ctx, void* stream, const pmp_pso_params* prm, const uint32_t* occ_bits, int n_plans,
+                  const int32_t* start, const int32_t* goal, const int32_t* init_positions, const int32_t* init_bounds,
+                  const double* rnd, int64_t rnd_stride, int32_t* status, int32_t* best_position, double* best_fitness,
+                  double* fitness_history, int32_t* positions, double* velocities, double* fitness,
+                  double* particle_best_fitness, double* points, double* length, int64_t* repeats,
+                  int32_t* trace_positions, double* trace_fitness);
+/* The most waves per workgroup pmp_pso_batch launches where pmp_pso_params.waves is 0.  No device call. */
+int pmp_pso_default_waves(void);
+
 /* Launch-span recording for profiling: while set, every A* 2D launch of this context folds its
  * workers' first start and last end wall-clock ticks into span[0] (atomic min) and span[1] (atomic
  * max); the caller initialises span to {UINT64_MAX, 0}.  NULL switches it off. */

@@ -95,6 +95,9 @@ SIGNATURES = {
     "pmp_bspline_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp,
                                _vp]),
     "pmp_cubic_spline_batch": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "pmp_pso_batch": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
+                           _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pmp_pso_default_waves": (_i, []),
 }
 
 
@@ -253,6 +256,15 @@ class BSplineParams(ctypes.Structure):
 class CubicSplineParams(ctypes.Structure):
     """pmp_cubic_spline_params == CubicSpline(step) (curve_generation/cubic_spline.py:26-27)."""
     _fields_ = [("step", ctypes.c_double), ("with_derivative", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+class PSOParams(ctypes.Structure):
+    """pmp_pso_params == the grid's ranges and PSO's n_particles, point_num, max_iter, weights and max_speed
+    (global_planner/evolutionary_search/pso.py:44-56); waves: wave64s per workgroup, 0 = the library's default."""
+    _fields_ = [("x_range", ctypes.c_int32), ("y_range", ctypes.c_int32), ("n_particles", ctypes.c_int32),
+                ("point_num", ctypes.c_int32), ("max_iter", ctypes.c_int32), ("waves", ctypes.c_int32),
+                ("w_inertial", ctypes.c_double), ("w_cognitive", ctypes.c_double), ("w_social", ctypes.c_double),
+                ("max_speed", ctypes.c_double)]
 
 
 TRACK_LQR, TRACK_MPC = 0, 1

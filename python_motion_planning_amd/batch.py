@@ -1439,3 +1439,68 @@ def cubic_spline_batch(curves, step: float, cost_only: bool = False, point_cap: 
     if retry_overflow and m and not cost_only:
         _retry_overflowed(torch, out, m, point_cap, row, rerun)
     return out
+
+
+def pso_default_waves() -> int:
+    """The wave64s per workgroup pmp_pso_batch launches unless told otherwise (csrc/pso.hip kDefaultWaves)."""
+    return int(_lib.load_library().pmp_pso_default_waves())
+
+
+def pso_draws(n_particles: int, point_num: int, max_iter: int) -> int:
+    """The random.random() draws of PSO.plan()'s iterations: two per point, particle and iteration."""
+    return 2 * int(point_num) * int(n_particles) * int(max_iter)
+
+
+def pso_batch(env_or_occ, starts, goals, init_positions, rnd, n_particles: int, point_num: int, max_iter: int,
+              w_inertial: float = 1.0, w_cognitive: float = 1.0, w_social: float = 1.0, max_speed: float = 6,
+              trace: bool = False, waves: int | None = None):
+    """Batched PSO.plan() after initializePositions() (global_planner/evolutionary_search/pso.py:77-123) on
+    pmp_pso_batch: one workgroup per plan, all plans on one grid.
+    env_or_occ: a Grid or a uint8 [W, H] occupancy; starts, goals [nq, 2] int; init_positions
+    [nq, n_particles, point_num, 2] int (initializePositions() of each plan); rnd [nq, stride] f64, each plan's
+    random.random() stream of at least pso_draws() values; waves: wave64s per workgroup (None: the default; the
+    results do not depend on it).
+    Returns dict of device tensors: status [nq] (4 where the best fitness is inf), best_position [nq, point_num, 2]
+    i32, best_fitness [nq], fitness_history [nq, max_iter], positions [nq, n_particles, point_num, 2] i32,
+    velocities (same shape, f64), fitness and particle_best_fitness [nq, n_particles], points [nq, 100, 2] and
+    length [nq] (the best particle's curve), repeats [nq] i64 (evaluations thrown away because an earlier particle
+    replaced the global best), and with trace: trace_positions [nq, max_iter, n_particles, point_num, 2] i32 and
+    trace_fitness [nq, max_iter, n_particles] (else None)."""
+    torch, L, ctx = _open()
+    entry = "pmp_pso_batch"
+    occ_bits, W, H = _occ2d(torch, env_or_occ)
+    s, g, nq = _endpoints(torch, starts, goals, 2, torch.int32)
+    n, pn, iters = int(n_particles), int(point_num), int(max_iter)
+    an, apn, ait = max(n, 0), max(pn, 0), max(iters, 0)  # what the outputs are sized by; the entry refuses the rest
+    if isinstance(init_positions, torch.Tensor):
+        init = _dev(torch, init_positions, torch.int32).reshape(-1, 2)
+        lo, hi = (init.amin(0).tolist(), init.amax(0).tolist()) if init.shape[0] else ([0, 0], [0, 0])
+    else:
+        host = np.ascontiguousarray(init_positions, dtype=np.int32).reshape(-1, 2)
+        lo, hi = (host.min(0).tolist(), host.max(0).tolist()) if len(host) else ([0, 0], [0, 0])
+        init = torch.as_tensor(host, device="cuda")
+    if n >= 1 and pn >= 1 and int(init.shape[0]) != nq * n * pn:
+        raise ValueError(f"{entry}: init_positions must be [nq, n_particles, point_num, 2]")
+    bounds = (ctypes.c_int32 * 4)(int(lo[0]), int(lo[1]), int(hi[0]), int(hi[1]))
+    rnd = _dev(torch, rnd, torch.float64).reshape(nq, -1) if nq else _dev(torch, rnd, torch.float64).reshape(0, 0)
+    prm = _lib.PSOParams(W, H, n, pn, iters, int(waves or 0), float(w_inertial), float(w_cognitive), float(w_social),
+                         float(max_speed))
+    f64 = dict(dtype=torch.float64, device="cuda")
+    i32 = dict(dtype=torch.int32, device="cuda")
+    out = dict(status=torch.empty(nq, **i32), best_position=torch.empty((nq, apn, 2), **i32),
+               best_fitness=torch.empty(nq, **f64), fitness_history=torch.empty((nq, ait), **f64),
+               positions=torch.empty((nq, an, apn, 2), **i32), velocities=torch.empty((nq, an, apn, 2), **f64),
+               fitness=torch.empty((nq, an), **f64), particle_best_fitness=torch.empty((nq, an), **f64),
+               points=torch.empty((nq, 100, 2), **f64), length=torch.empty(nq, **f64),
+               repeats=torch.empty(nq, dtype=torch.int64, device="cuda"),
+               trace_positions=torch.empty((nq, ait, an, apn, 2), **i32) if trace else None,
+               trace_fitness=torch.empty((nq, ait, an), **f64) if trace else None)
+    rc = L.pmp_pso_batch(ctx, _lib.stream_ptr(), ctypes.byref(prm), occ_bits.data_ptr(), nq, s.data_ptr(), g.data_ptr(),
+                         init.data_ptr(), bounds, rnd.data_ptr(), int(rnd.shape[1]), out["status"].data_ptr(),
+                         out["best_position"].data_ptr(), out["best_fitness"].data_ptr(),
+                         out["fitness_history"].data_ptr(), out["positions"].data_ptr(), out["velocities"].data_ptr(),
+                         out["fitness"].data_ptr(), out["particle_best_fitness"].data_ptr(), out["points"].data_ptr(),
+                         out["length"].data_ptr(), out["repeats"].data_ptr(), _lib.ptr(out["trace_positions"]),
+                         _lib.ptr(out["trace_fitness"]))
+    _lib.check(ctx, rc, entry)
+    return out

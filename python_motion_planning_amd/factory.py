@@ -5,7 +5,7 @@ reference planners outside the accelerated hot path raise NotImplementedError (n
 substituted)."""
 from __future__ import annotations
 
-_SEARCH_OUT_OF_SCOPE = {"jps", "voronoi", "s_theta_star", "anya", "rrt_connect", "aco", "pso"}
+_SEARCH_OUT_OF_SCOPE = {"jps", "voronoi", "s_theta_star", "anya", "rrt_connect", "aco"}
 # PID / APF / RPP exist as classes (local_planner.PID, APF, RPP); like "jps", their factory names keep
 # raising (DESIGN.md section 6)
 _CONTROL_OUT_OF_SCOPE = {"pid", "apf", "rpp"}
@@ -25,6 +25,10 @@ class SearchFactory(object):
             if cls is None:
                 raise NotImplementedError(f"{planner_name} is not implemented yet in python_motion_planning_amd")
             return cls(**config)
+        if planner_name == "pso":
+            from . import evolutionary_search
+
+            return evolutionary_search.PSO(**config)
         if planner_name in _SEARCH_OUT_OF_SCOPE:
             raise NotImplementedError(f"{planner_name} is outside the accelerated hot path of python_motion_planning_amd")
         raise ValueError("The `planner_name` must be set correctly.")
