@@ -39,6 +39,7 @@ extern "C" {
 #define PMP_PATH_OVERFLOW 2
 #define PMP_CAP_OVERFLOW 3
 #define PMP_REF_RAISES 4
+#define PMP_REF_INDEX_ERROR 5 /* pmp_aco_batch: the reference's roulette indexes past its list (IndexError) */
 
 typedef struct pmp_ctx pmp_ctx;
 
@@ -1042,6 +1043,66 @@ int pmp_pso_batch(pmp_ctx* ctx, void* stream, const pmp_pso_params* prm, const u
                   int32_t* trace_positions, double* trace_fitness);
 /* The most waves per workgroup pmp_pso_batch launches where pmp_pso_params.waves is 0.  No device call. */
 int pmp_pso_default_waves(void);
+
+/* ACO(start, goal, env, n_ants, alpha, beta, rho, Q, max_iter) (global_planner/evolutionary_search/aco.py:40-49)
+ * and the grid's ranges.  beta is in the caller's heuristic table, rho is passed as the host's own 1 - rho */
+typedef struct {
+    int32_t x_range, y_range;
+    int32_t n_ants;
+    int32_t max_iter;
+    int32_t waves;    /* wave64s (plans) per workgroup, 1..8; 0 = pmp_aco_default_waves().  Results do not depend on it */
+    int32_t reserved;
+    double alpha;     /* 1.0 (pheromone ** 1.0 is the pheromone) or 0.0 (it is 1.0) */
+    double one_minus_rho;
+    double Q;
+} pmp_aco_params;
+
+/*
+ * Batched ant-colony plans on one grid.  Replaces ACO.plan() (aco.py:65-166) for n_plans independent plans in
+ * one launch, one wave64 per plan: max_iter iterations of n_ants ants, each walking from the start over open,
+ * unvisited neighbours by roulette (one random.random() per step, drawn by MT19937 in the kernel from the
+ * plan's state) until it stands next to the goal, has no candidate with a non-zero weight, or has made
+ * ceil(x_range y_range / 2 + max(x_range, y_range)) choices; then the evaporation, the successful ants'
+ * deposits in ant order and the reference's bookkeeping of the best path.  Every operation on doubles is the
+ * reference's, in its order, so the walk, the pheromone and the generator's state are the reference's bit for
+ * bit.  An edge is (cell, motion index m), env.motions order (-1,0) (-1,1) (0,1) (1,1) (1,0) (1,-1) (0,-1) (-1,-1).
+ *   occ_bits: the grid's bit-packed x-major occupancy (cell x * y_range + y), as for pmp_astar2d_batch
+ *   starts, goals [n_plans][2] i32
+ *   heur [n_tables][x_range y_range] f64: (1.0 / h(cell, goal)) ** beta by the host's own pow, any finite value
+ *       for the goal and the obstacles (never read into a sum); heur_of [n_plans] i32: each plan's table
+ *   mt_state_in [n_plans][625] u32: random.getstate()[1], the 624 words and the index
+ *   status [n_plans]: 0 a path, 1 no ant ever found the goal, 5 the roulette's draw exceeded its last cumulative
+ *       quotient (the reference raises IndexError): the plan stops there, the generator just after that draw
+ *   best_len [n_plans], best_path [n_plans][cap] i32 cell ids, start first, cap = pmp_aco_path_cap()
+ *       (entries from best_len on are not written: what an earlier, longer best path left, or the caller's fill)
+ *   n_cost [n_plans], cost_list [n_plans][max_iter] i32: an entry per iteration from the first successful one
+ *   draws [n_plans] i64; mt_state_out [n_plans][625]
+ *   ant_found, ant_len [n_plans][max_iter][n_ants] i32, nullable together: every ant's found_goal and len(path)
+ *   pheromone [n_plans][x_range y_range][8] f64: the plan's pheromone, final on return (1.0 evaporated and
+ *       deposited on for an open edge, 0.0 for the others)
+ *   paths [n_plans][n_ants][cap] u16 and ant_scratch [n_plans][n_ants] i32: scratch
+ * The entry checks the device-resident inputs with a small kernel and waits for its verdict: one
+ * synchronisation of the stream per call, so it cannot be captured into a graph.
+ * Refused with PMP_EINVAL: alpha other than 0.0 or 1.0; n_ants < 1; max_iter < 0; a non-finite one_minus_rho, Q
+ * or heur entry of a free cell; a start or goal outside the grid or in an obstacle; heur_of outside the tables;
+ * more than 65,536 cells; waves outside 0..8; an MT index above 624; a free cell on the grid's border (the
+ * reference's ant steps outside the grid there and dies with KeyError one step later); null pointers;
+ * n_plans < 0.
+ */
+int pmp_aco_batch(pmp_ctx* ctx, void* stream, const pmp_aco_params* prm, const uint32_t* occ_bits, int n_plans,
+                  const int32_t* starts, const int32_t* goals, const double* heur, int n_tables, const int32_t* heur_of,
+                  const uint32_t* mt_state_in, int32_t* status, int32_t* best_len, int32_t* best_path, int32_t* n_cost,
+                  int32_t* cost_list, int64_t* draws, uint32_t* mt_state_out, int32_t* ant_found, int32_t* ant_len,
+                  double* pheromone, uint16_t* paths, int32_t* ant_scratch);
+/* Waves per workgroup where pmp_aco_params.waves is 0, and the most it takes.  No device call. */
+int pmp_aco_default_waves(void);
+int pmp_aco_max_waves(void);
+/* Entries of a path: ceil(x_range y_range / 2 + max(x_range, y_range)) + 1; 0 for a grid the entry refuses */
+int pmp_aco_path_cap(int x_range, int y_range);
+/* The next n values of random.random() from state_in [625] (random.getstate()[1]; an index above 624 is read
+ * as 624) into out [n], and the state after them into state_out [625]: mt19937_dev.h's generator on its own.
+ * All device pointers; one wave.  Refused with PMP_EINVAL: n < 0; null pointers. */
+int pmp_mt19937_doubles(pmp_ctx* ctx, void* stream, const uint32_t* state_in, int64_t n, double* out, uint32_t* state_out);
 
 /* Launch-span recording for profiling: while set, every A* 2D launch of this context folds its
  * workers' first start and last end wall-clock ticks into span[0] (atomic min) and span[1] (atomic

@@ -98,6 +98,12 @@ SIGNATURES = {
     "pmp_pso_batch": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
                            _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmp_pso_default_waves": (_i, []),
+    "pmp_aco_batch": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                           _vp, _vp, _vp]),
+    "pmp_aco_default_waves": (_i, []),
+    "pmp_aco_max_waves": (_i, []),
+    "pmp_aco_path_cap": (_i, [_i, _i]),
+    "pmp_mt19937_doubles": (_i, [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp]),
 }
 
 
@@ -267,6 +273,14 @@ class PSOParams(ctypes.Structure):
                 ("max_speed", ctypes.c_double)]
 
 
+class ACOParams(ctypes.Structure):
+    """pmp_aco_params == the grid's ranges and ACO's n_ants, max_iter, alpha, 1 - rho and Q
+    (global_planner/evolutionary_search/aco.py:40-49); waves: plans per workgroup, 0 = the library's default."""
+    _fields_ = [("x_range", ctypes.c_int32), ("y_range", ctypes.c_int32), ("n_ants", ctypes.c_int32),
+                ("max_iter", ctypes.c_int32), ("waves", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("alpha", ctypes.c_double), ("one_minus_rho", ctypes.c_double), ("Q", ctypes.c_double)]
+
+
 TRACK_LQR, TRACK_MPC = 0, 1
 
 
@@ -291,6 +305,7 @@ FOLLOW_PID, FOLLOW_APF, FOLLOW_RPP = 0, 1, 2
 FOLLOW_KINDS = {"pid": FOLLOW_PID, "apf": FOLLOW_APF, "rpp": FOLLOW_RPP}
 
 STATUS_FOUND, STATUS_NO_PATH, STATUS_PATH_OVERFLOW, STATUS_CAP_OVERFLOW, STATUS_REF_RAISES = range(5)
+STATUS_REF_INDEX_ERROR = 5  # pmp_aco_batch: the reference's roulette raises IndexError
 
 
 class PMPError(RuntimeError):

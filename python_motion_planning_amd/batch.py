@@ -1504,3 +1504,96 @@ def pso_batch(env_or_occ, starts, goals, init_positions, rnd, n_particles: int, 
                          _lib.ptr(out["trace_fitness"]))
     _lib.check(ctx, rc, entry)
     return out
+
+
+def aco_default_waves() -> int:
+    """The wave64s (plans) per workgroup pmp_aco_batch launches unless told otherwise (csrc/aco.hip kDefaultWaves)."""
+    return int(_lib.load_library().pmp_aco_default_waves())
+
+
+def aco_max_waves() -> int:
+    """The most waves per workgroup pmp_aco_batch takes."""
+    return int(_lib.load_library().pmp_aco_max_waves())
+
+
+def aco_path_cap(x_range: int, y_range: int) -> int:
+    """Entries of an ant's path: ceil(x_range * y_range / 2 + max(x_range, y_range)) choices (aco.py:86, :95) and
+    the goal.  No library call: the same rule as pmp_aco_path_cap."""
+    return math.ceil(x_range * y_range / 2 + max(x_range, y_range)) + 1
+
+
+def _mt_words(torch, states):
+    """[n, 625] uint32 state words (as int32 bits) on the device, from arrays or random.getstate() tuples"""
+    rows = [np.asarray(s[1] if isinstance(s, tuple) and len(s) == 3 and isinstance(s[1], tuple) else s, np.uint32)
+            for s in states]
+    a = np.ascontiguousarray(np.stack(rows)) if rows else np.zeros((0, 625), np.uint32)
+    if a.ndim != 2 or a.shape[1] != 625:
+        raise ValueError("an MT19937 state is 624 words and the index")
+    return torch.as_tensor(a.view(np.int32), device="cuda")
+
+
+def mt19937_doubles(state, n: int):
+    """The next n values of random.random() from `state` (a random.getstate() tuple or its 625 words) by the
+    kernels' generator (csrc/mt19937_dev.h, pmp_mt19937_doubles).  Returns (device f64 [n], numpy uint32 [625]
+    state after them)."""
+    torch, L, ctx = _open()
+    words = _mt_words(torch, [state])
+    out = torch.empty(max(int(n), 0), dtype=torch.float64, device="cuda")
+    after = torch.empty(625, dtype=torch.int32, device="cuda")
+    rc = L.pmp_mt19937_doubles(ctx, _lib.stream_ptr(), words.data_ptr(), int(n), out.data_ptr(), after.data_ptr())
+    _lib.check(ctx, rc, "pmp_mt19937_doubles")
+    return out, after.cpu().numpy().view(np.uint32)
+
+
+def aco_batch(env_or_occ, starts, goals, heur, heur_of, mt_states, n_ants: int = 50, max_iter: int = 100,
+              alpha: float = 1.0, one_minus_rho: float = 0.9, Q: float = 1.0, trace: bool = False,
+              waves: int | None = None):
+    """Batched ACO.plan() (global_planner/evolutionary_search/aco.py:65-166) on pmp_aco_batch: one wave64 per
+    plan, all plans on one grid, the random.random() draws made in the kernel.
+    env_or_occ: a Grid or a uint8 [W, H] occupancy; starts, goals [nq, 2] int; heur [n_tables, W * H] f64, the
+    host's (1.0 / h(cell, goal)) ** beta per cell x * H + y (finite for every free cell); heur_of [nq] int, each
+    plan's table; mt_states: per plan a random.getstate() tuple or its 625 words; one_minus_rho: the host's
+    1 - rho; waves: plans per workgroup (None: the default; the results do not depend on it).
+    Scratch per plan, allocated here: the pheromone, W * H * 64 bytes; the iteration's paths, n_ants *
+    aco_path_cap(W, H) * 2 bytes (a default plan on the 51 x 31 map: 50 ants x 843 entries, 84 KB, beside 101 KB
+    of pheromone); 4 * n_ants bytes of lengths.
+    Returns dict of device tensors: status [nq] (0 a path, 1 no ant found the goal, 5 the reference raises
+    IndexError), best_len [nq], best_path [nq, cap] i32 cell ids (start first; past best_len zeros or what an
+    earlier, longer best path left), n_cost [nq], cost_list
+    [nq, max_iter] i32, draws [nq] i64, mt_state_out [nq, 625] (uint32 bits in int32), and with trace ant_found,
+    ant_len [nq, max_iter, n_ants] i32 and pheromone [nq, W * H, 8] f64 (else None)."""
+    torch, L, ctx = _open()
+    entry = "pmp_aco_batch"
+    occ_bits, W, H = _occ2d(torch, env_or_occ)
+    s, g, nq = _endpoints(torch, starts, goals, 2, torch.int32)
+    na, it = int(n_ants), int(max_iter)
+    ana, ait = max(na, 0), max(it, 0)  # what the outputs are sized by; the entry refuses the rest
+    cells = W * H
+    cap = int(L.pmp_aco_path_cap(W, H))
+    heur = _dev(torch, heur, torch.float64).reshape(-1, max(cells, 1))
+    heur_of = _dev(torch, heur_of, torch.int32).reshape(-1)
+    states = mt_states if isinstance(mt_states, torch.Tensor) else _mt_words(torch, mt_states)
+    states = states.to(device="cuda", dtype=torch.int32).contiguous().reshape(-1, 625)
+    if int(heur_of.shape[0]) != nq or int(states.shape[0]) != nq:
+        raise ValueError(f"{entry}: heur_of and mt_states must have one entry per plan")
+    prm = _lib.ACOParams(W, H, na, it, int(waves or 0), 0, float(alpha), float(one_minus_rho), float(Q))
+    i32 = dict(dtype=torch.int32, device="cuda")
+    out = dict(status=torch.empty(nq, **i32), best_len=torch.empty(nq, **i32), best_path=torch.zeros((nq, max(cap, 1)), **i32),
+               n_cost=torch.empty(nq, **i32), cost_list=torch.zeros((nq, ait), **i32),
+               draws=torch.empty(nq, dtype=torch.int64, device="cuda"), mt_state_out=torch.empty((nq, 625), **i32),
+               ant_found=torch.zeros((nq, ait, ana), **i32) if trace else None,
+               ant_len=torch.zeros((nq, ait, ana), **i32) if trace else None)
+    big = cap > 0  # a grid the entry refuses gets no scratch
+    pher = torch.empty((nq, cells if big else 1, 8), dtype=torch.float64, device="cuda")
+    paths = torch.empty((nq, ana, cap if big else 1), dtype=torch.int16, device="cuda")
+    lens = torch.empty((nq, max(ana, 1)), **i32)
+    rc = L.pmp_aco_batch(ctx, _lib.stream_ptr(), ctypes.byref(prm), occ_bits.data_ptr(), nq, s.data_ptr(), g.data_ptr(),
+                         heur.data_ptr(), int(heur.shape[0]), heur_of.data_ptr(), states.data_ptr(),
+                         out["status"].data_ptr(), out["best_len"].data_ptr(), out["best_path"].data_ptr(),
+                         out["n_cost"].data_ptr(), out["cost_list"].data_ptr(), out["draws"].data_ptr(),
+                         out["mt_state_out"].data_ptr(), _lib.ptr(out["ant_found"]), _lib.ptr(out["ant_len"]),
+                         pher.data_ptr(), paths.data_ptr(), lens.data_ptr())
+    _lib.check(ctx, rc, entry)
+    out["pheromone"] = pher if trace else None
+    out["W"], out["H"] = W, H
+    return out

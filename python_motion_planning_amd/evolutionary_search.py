@@ -1,5 +1,7 @@
 """Evolutionary global planners: drop-in for global_planner/evolutionary_search/ (evolutionary_search.py:11-87,
-pso.py:18-356).  PSO.plan() runs the whole swarm in one launch of pmp_pso_batch (csrc/pso.hip): the initial
+pso.py:18-356, aco.py:14-186).  ACO.plan() runs the whole colony in one launch of pmp_aco_batch (csrc/aco.hip),
+which draws from MT19937 itself: the draw count depends on every earlier draw, so the generator's state goes in
+and comes back.  PSO.plan() runs the whole swarm in one launch of pmp_pso_batch (csrc/pso.hip): the initial
 positions are drawn on the host from the global `random` (their draw count depends on the draws), the
 iterations' draws, whose count is fixed, are handed to the kernel as a stream.
 
@@ -15,6 +17,7 @@ import random
 import numpy as np
 
 from . import batch
+from ._lib import STATUS_REF_INDEX_ERROR
 from .curve import BSpline
 from .env import Grid, Node
 from .planner import Planner
@@ -270,3 +273,147 @@ class PSO(EvolutionarySearcher):
             if (x, y) in self.obstacles:
                 return True
         return False
+
+
+def aco_max_steps(x_range: int, y_range: int) -> float:
+    """ACO's step cap (aco.py:86), a float: an ant makes choices while steps < it."""
+    return x_range * y_range / 2 + max(x_range, y_range)
+
+
+def _aco_table(planner, goal: Node, beta: float) -> np.ndarray:
+    """[W * H] f64, cell x * H + y: (1.0 / h(cell, goal)) ** beta by the planner's own h() and CPython's own **
+    for every free cell but the goal (aco.py:118); 0.0 for the goal and the obstacles, which enter no sum."""
+    W, H = planner.env.x_range, planner.env.y_range
+    obs = planner.obstacles
+    tab = np.zeros(W * H, np.float64)
+    for x in range(W):
+        for y in range(H):
+            if (x, y) in obs or (x, y) == goal.current:
+                continue
+            tab[x * H + y] = (1.0 / planner.h(Node((x, y), (x, y), 0, 0), goal)) ** beta
+    return tab
+
+
+def _aco_check(env: Grid, alpha: float) -> None:
+    """What ACO.plan() refuses before anything touches the device"""
+    if alpha not in (0.0, 1.0):
+        raise NotImplementedError("ACO on the device takes alpha 0.0 or 1.0 only: pheromone ** alpha is then the "
+                                  "pheromone or 1.0 bit for bit, and there is no bit-reproducible device pow")
+    W, H = env.x_range, env.y_range
+    obs = env.obstacles
+    if any((x, y) not in obs for x in range(W) for y in (0, H - 1)) or \
+            any((x, y) not in obs for y in range(H) for x in (0, W - 1)):
+        raise ValueError("ACO needs every border cell of the grid to be an obstacle: from a free one the reference's "
+                         "ant steps outside the grid and dies with KeyError one step later")
+
+
+class ACO(EvolutionarySearcher):
+    """Ant Colony Optimization(ACO) motion planning (aco.py:14-186); the colony runs on the device, one wave per
+    plan, with the random.random() draws made in the kernel from the global generator's state.
+
+    Parameters:
+        start (tuple), goal (tuple), env (Grid), heuristic_type (str): as EvolutionarySearcher
+        n_ants (int): number of ants
+        alpha (float), beta (float): pheromone and heuristic factor weight coefficients.  plan() takes alpha 0.0
+            or 1.0 (NotImplementedError otherwise); beta goes into a table built on the host
+        rho (float): evaporation coefficient
+        Q (float): pheromone gain
+        max_iter (int): maximum iterations
+
+    Grids of more than 65,536 cells and grids with a free border cell are refused.
+    """
+
+    def __init__(self, start: tuple, goal: tuple, env: Grid, heuristic_type: str = "euclidean",
+                 n_ants: int = 50, alpha: float = 1.0, beta: float = 5.0, rho: float = 0.1, Q: float = 1.0,
+                 max_iter: int = 100) -> None:
+        super().__init__(start, goal, env, heuristic_type)
+        self.n_ants = n_ants
+        self.alpha = alpha
+        self.beta = beta
+        self.rho = rho
+        self.Q = Q
+        self.max_iter = max_iter
+        self.draws = None  # after plan(): the random.random() calls it made
+
+    def __str__(self) -> str:
+        return "Ant Colony Optimization(ACO)"
+
+    class Ant:
+        def __init__(self) -> None:
+            self.reset()
+
+        def reset(self) -> None:
+            self.found_goal = False
+            self.current_node = None
+            self.path = []
+            self.path_set = set()
+            self.steps = 0
+
+    def heuristic_table(self) -> np.ndarray:
+        """(1.0 / h(cell, goal)) ** beta per cell x * y_range + y, as plan() hands it to the kernel.  Python's own
+        OverflowError propagates where beta makes a cell overflow (the reference raises only when an ant gets
+        there)."""
+        return _aco_table(self, self.goal, self.beta)
+
+    def plan(self) -> tuple:
+        """(cost, path [(x, y), ...], cost_list) or ([], [], []) where no ant found the goal (aco.py:65-166): one
+        launch.  The global `random` ends where the reference's draws would leave it; IndexError where the
+        reference's roulette raises it."""
+        _aco_check(self.env, self.alpha)
+        table = self.heuristic_table()
+        version, _, gauss_next = state = random.getstate()
+        out = batch.aco_batch(self.env, [self.start.current], [self.goal.current], table[None], [0], [state],
+                              self.n_ants, self.max_iter, self.alpha, 1 - self.rho, self.Q)
+        status, n, n_cost = int(out["status"][0]), int(out["best_len"][0]), int(out["n_cost"][0])
+        words = out["mt_state_out"][0].cpu().numpy().view(np.uint32)
+        random.setstate((version, tuple(int(w) for w in words), gauss_next))
+        self.draws = int(out["draws"][0])
+        if status == STATUS_REF_INDEX_ERROR:
+            raise IndexError("list index out of range")
+        if status != 0:
+            return [], [], []
+        H = self.env.y_range
+        cells = out["best_path"][0, :n].cpu().numpy()
+        nodes = [Node((int(c) // H, int(c) % H)) for c in cells]
+        cost = 0
+        path = [self.start.current]
+        for i in range(len(nodes) - 1):
+            cost += self.dist(nodes[i], nodes[i + 1])
+            path.append(nodes[i + 1].current)
+        return cost, path, [int(v) for v in out["cost_list"][0, :n_cost].cpu().numpy()]
+
+    @staticmethod
+    def plan_batch(env: Grid, starts, goals, seeds_or_states, heuristic_type: str = "euclidean", n_ants: int = 50,
+                   alpha: float = 1.0, beta: float = 5.0, rho: float = 0.1, Q: float = 1.0, max_iter: int = 100, **kw):
+        """Independent plans on one Grid in one launch.  seeds_or_states: per plan an int (random.seed's) or a
+        random.getstate() tuple; each plan draws from a generator of its own, as ACO(...).plan() does after
+        random.seed(seed).  Plans with the same goal share one heuristic table.  Returns batch.aco_batch's
+        device-tensor dict with heur_of (numpy [nq], each plan's table) and random_states (each generator's
+        state after its plan; reads the states back) added."""
+        _aco_check(env, alpha)
+        probe = ACO((0, 0), (0, 0), env, heuristic_type)
+        states, tables, index, heur_of = [], [], {}, []
+        for g, seed in zip(goals, seeds_or_states):
+            states.append(seed if isinstance(seed, tuple) else random.Random(seed).getstate())
+            g = tuple(int(v) for v in g)
+            if g not in index:
+                index[g] = len(tables)
+                tables.append(_aco_table(probe, Node(g, g, 0, 0), beta))
+            heur_of.append(index[g])
+        out = batch.aco_batch(env, np.asarray(starts, np.int32), np.asarray(goals, np.int32),
+                              np.asarray(tables, np.float64).reshape(len(tables), -1), np.asarray(heur_of, np.int32),
+                              states, n_ants, max_iter, alpha, 1 - rho, Q, **kw)
+        words = out["mt_state_out"].cpu().numpy().view(np.uint32)
+        out["heur_of"] = np.asarray(heur_of, np.int32)
+        out["random_states"] = [(st[0], tuple(int(w) for w in row), st[2]) for st, row in zip(states, words)]
+        return out
+
+    def getNeighbor(self, node: Node) -> list:
+        """The neighbours of node the class's isCollision lets it move to, in motion order (aco.py:168-179); on
+        the host."""
+        return [node + motion for motion in self.motions if not self.isCollision(node, node + motion)]
+
+    def run(self):
+        """Reference: plan() and its animation.  Animation is out of scope; returns plan()'s result."""
+        return self.plan()
+

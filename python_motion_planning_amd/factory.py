@@ -5,6 +5,8 @@ reference planners outside the accelerated hot path raise NotImplementedError (n
 substituted)."""
 from __future__ import annotations
 
+# "aco" has a class (evolutionary_search.ACO, csrc/aco.hip) but, like "jps" and "rrt_connect", its factory name
+# keeps raising: construct the class (DESIGN.md section 6)
 _SEARCH_OUT_OF_SCOPE = {"jps", "voronoi", "s_theta_star", "anya", "rrt_connect", "aco"}
 # PID / APF / RPP exist as classes (local_planner.PID, APF, RPP); like "jps", their factory names keep
 # raising (DESIGN.md section 6)
